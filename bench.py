@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the GeoBO GP joint-inversion hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 64] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 64] [--dump-outputs DIR] [--full [--no-cpu]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, the stage tables and `roofline` /
+`roofline_factorisation` of the timed steps themselves).  `--full` adds what needs work of its own: `parity_vs_oracle_sample`,
+`roofline_assembly` and `cpu_baseline` (the last one not with `--no-cpu`).  `--dump-outputs DIR` writes the last timed step's cubes
+(and the log-likelihood) as DIR/<name>.npy; the inputs are fixed by the arguments, so two builds can be compared output by output.
 
 A "step" is one full pass of the hot path over one synthetic survey: everything about the forward operators A_g/A_m that the
 route needs built on the device (stencil tables + boundary slabs on a lattice survey -- no operator is materialised there --, incl.
@@ -21,7 +26,7 @@ HIP-event time of each collective per step is reported as `config.collective_ms_
 table; `--check` re-runs the problem on rank 0 alone inside the same job and compares the cubes.  (Surveys off the lattice and the
 dense method keep the round-2 forms: voxel-column shards, all-reduce of the partial AkA or all-to-all of A K block-columns.)
 
-Prints ONE JSON line on rank 0 (see the driver contract); extra objects:
+Prints ONE JSON line on rank 0 (see the driver contract); extra objects (`--full` only: roofline_assembly, cpu_baseline):
   roofline      dominant kernel = geobo_spectral_y on the default route (the y stage of every covariance product, as an in-kernel spectral
                 product on the matrix pipe since round 6; HBM-bound, fp64 pipe co-bound): ALGORITHMIC bytes per launch (spectrum read once +
                 one output slab per property block) / mean launch duration measured with HIP events on the launch stream, against 8 TB/s.  (GEOBO_POSTERIOR=dense:
@@ -293,6 +298,29 @@ def cpu_baseline_forms(sizes, dense_sizes, F64, gflops_sample):
     return forms
 
 
+OUTPUT_NAMES = ("mu_density", "mu_magsus", "mu_drill", "var_density", "var_magsus", "var_drill")
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_HEADER_MARGIN = 4096     # .npy headers (128 B each) and logl
+
+
+def dump_outputs(d, cubes, logl, props):
+    """What a caller of the timed path receives from its last step: the posterior cubes of the computed property blocks (the drill
+    blocks only with --props 3) and the log-likelihood, float64.  Above DUMP_LIMIT_BYTES every cube is cut to the same voxels, a
+    sorted sample drawn with a fixed seed, written alongside as sample_voxels.npy (flat C-order indices, float64)."""
+    os.makedirs(d, exist_ok=True)
+    idx = (0, 1, 3, 4) if props == 2 else range(6)
+    arrs = {OUTPUT_NAMES[i]: np.ascontiguousarray(cubes[i], dtype=np.float64) for i in idx}
+    n = next(iter(arrs.values())).size
+    if sum(v.nbytes for v in arrs.values()) + DUMP_HEADER_MARGIN > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - DUMP_HEADER_MARGIN) // (8 * (len(arrs) + 1))
+        sel = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        arrs = {name: v.reshape(-1)[sel] for name, v in arrs.items()}
+        arrs["sample_voxels"] = sel.astype(np.float64)
+    arrs["logl"] = np.array([logl], dtype=np.float64)
+    for name, v in arrs.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
 def relaunch_with_ranks(a):
     """`python bench.py --gpus N` without a launcher in the environment: start the N ranks ourselves (one process per GPU,
     torch.distributed.run, rendezvous on 127.0.0.1) and exit with their status."""
@@ -326,7 +354,11 @@ def main():
                     "covariance tables in fp32, fp64 accumulation and factorisation); NOT the headline configuration")
     ap.add_argument("--operators", default="auto", choices=["auto", "resident", "streamed"],
                     help="auto (the library default): no materialised operators where the lattice forms make them unnecessary")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the measurements that need work of their own: comparison with the "
+                    "oracle's golden sample, the assembly roofline (launches of its own) and the CPU baseline (unless --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the cubes and the log-likelihood of the last "
+                    "step as DIR/<name>.npy (float64; a fixed seeded sample of voxels above 64e6 bytes)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--cpu-forms", default="16,32", help="comma list of cube edges for the full matrix-free CPU oracle step "
                     "(SURVEY 8(d) form (b)); the 64^3 figure is extrapolated from the LARGEST one (32^3: ~1 min on the box's 128 threads)")
     ap.add_argument("--cpu-dense-forms", default="16", help="cube edges for the reference-shaped CPU form (a) of SURVEY 8(d): full K and full "
@@ -382,7 +414,8 @@ def main():
     # ~3000 voxels spread over the cube -- padded slabs, faces, corners, every drilled voxel -- from the oracle's own operators, FFT rows
     # of A K, scipy Cholesky; nothing of the device in it).  Its survey is the same synthetic model through the ORACLE's operators
     # (float32-rounded like the GeoTIFF path; the device's own A rho differs from it in the last float32 bit of a few values), so the
-    # timed steps run on THAT survey and the line carries the comparison (`parity_vs_oracle_sample`).
+    # timed steps run on THAT survey (plain runs too: the inputs do not depend on --full) and the --full line carries the comparison
+    # (`parity_vs_oracle_sample`).
     golden = None
     gpath = os.path.join(ROOT, "tests", "golden", "oracle64_sample_matern32.npz")
     if n == 64 and a.kernel == "matern32" and a.drill == 50 and a.assembly == "f64" and os.path.exists(gpath):
@@ -422,6 +455,8 @@ def main():
         marks.append(time.perf_counter())
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, cubes, inv.logl, a.props)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -640,7 +675,7 @@ def main():
                        "kernel_tflops_executed_rank0": {k: round(v["flop"] / v["seconds"] / 1e12, 2) for k, v in stages.items() if v["flop"] > 0}},
             "roofline": roof,
         }
-        if golden is not None:
+        if golden is not None and a.full:
             q, N_ = golden["voxels"], eng.N
             var_all = inv.cov_rec.diagonal()
             nrm = lambda got, want: float(np.abs(got - want).max() / np.abs(want).max())
@@ -652,11 +687,11 @@ def main():
                 "mean_normwise": [nrm(inv.mu_rec[j * N_ + q], golden["mu"][j]) for j in (0, 1)],
                 "variance_max_abs": [float(np.abs(var_all[j * N_ + q] - golden["var"][j]).max()) for j in (0, 1)],
                 "logl_rel": float(abs(inv.logl - float(golden["logl"])) / abs(float(golden["logl"]))), "tolerance": "1e-8 (north_star)"}
-        if world == 1 and a.assembly == "f64":
+        if a.full and world == 1 and a.assembly == "f64":
             out["roofline_assembly"] = assembly_roofline(inv, [float(v) for v in inv.gp_length])
         if "potrf_inv" in stages and stages["potrf_inv"]["flop"] > 0:
             out["roofline_factorisation"] = factorisation_roofline(stages["potrf_inv"], a.steps)
-        if not a.no_cpu and world == 1:   # CPU baseline: rank 0 at N = 1 only
+        if a.full and not a.no_cpu and world == 1:   # CPU baseline: rank 0 at N = 1 only
             lengths = inv.gp_length
             cb, (cols, smp) = cpu_baseline(inv, [float(v) for v in lengths])
             cb["sample_max_abs_diff_vs_gpu_mu"] = float(np.abs(smp[0][0] - inv.mu_rec[cols]).max())

@@ -160,7 +160,7 @@ def _rows_worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 4])
+@pytest.mark.parametrize("world", [2, 4, 8])
 def test_row_sharded_transposed_posterior_matches_reference(world):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
