@@ -80,6 +80,8 @@ SIGNATURES = {
     "geobo_potrf_inv": (_int, [_i64, _dp, _i64, _dp, _i64, _dp, _dp, _sz, _dp, _dp]),
     "geobo_posterior_ws_bytes": (_sz, [_i64, _i64]),
     "geobo_posterior_reduce": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _dp, _f64, _dp, _dp, _i64, _dp, _sz, _dp]),
+    "geobo_kinv_dot_ws_bytes": (_sz, [_i64, _int]),
+    "geobo_kinv_dot": (_int, [_i64, _dp, _i64, _dp, _int, C.POINTER(_dp), _i64, C.POINTER(_i64), _dp, _dp, _sz, _dp]),
     "geobo_trmv_stats": (_int, [_i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _dp]),
     "geobo_mfma_f64_peak": (_int, [_int, _int, _dp, _dp]),
     "geobo_mfma_mix": (_int, [_int, _int, _int, _int, _dp, _dp]),

@@ -465,7 +465,7 @@ extern "C" int geobo_k_block(int kernel_id, const double* rx, const double* ry, 
   const dim3 grid((unsigned)((nc + 511) / 512), (unsigned)((nr + KB_ROWS - 1) / KB_ROWS));
   hipStream_t st = (hipStream_t)stream;
 #define GEOBO_KB(ID) hipLaunchKernelGGL((k_block_kernel<ID, double>), grid, dim3(256), 0, st, rx, ry, rz, nr, cx, cy, cz, nc, p, out, ld)
-  COV_DISPATCH(kernel_id, GEOBO_KB);
+  COV_DISPATCH_ALL(kernel_id, GEOBO_KB);
 #undef GEOBO_KB
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }
@@ -480,7 +480,7 @@ extern "C" int geobo_k_block_f32(int kernel_id, const double* rx, const double* 
   const dim3 grid((unsigned)((nc + 511) / 512), (unsigned)((nr + KB_ROWS - 1) / KB_ROWS));
   hipStream_t st = (hipStream_t)stream;
 #define GEOBO_KB(ID) hipLaunchKernelGGL((k_block_kernel<ID, float>), grid, dim3(256), 0, st, rx, ry, rz, nr, cx, cy, cz, nc, p, out, ld)
-  COV_DISPATCH(kernel_id, GEOBO_KB);
+  COV_DISPATCH_ALL(kernel_id, GEOBO_KB);
 #undef GEOBO_KB
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }
@@ -584,7 +584,7 @@ extern "C" int geobo_cov_table(int kernel_id, int nx, int ny, int nz, double sx,
   if (nb > 4096) nb = 4096;
   hipStream_t st = (hipStream_t)stream;
 #define GEOBO_CT(ID) hipLaunchKernelGGL(cov_table_kernel<ID>, dim3((unsigned)nb), dim3(256), 0, st, nx, ny, nz, sx, sy, sz, p, table)
-  COV_DISPATCH(kernel_id, GEOBO_CT);
+  COV_DISPATCH_ALL(kernel_id, GEOBO_CT);
 #undef GEOBO_CT
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }
@@ -598,7 +598,7 @@ extern "C" int geobo_k_eval(int kernel_id, const double* d2, int64_t n, double l
   if (nb > 256 * 16) nb = 256 * 16;
   hipStream_t st = (hipStream_t)stream;
 #define GEOBO_KE(ID) hipLaunchKernelGGL(k_eval_kernel<ID>, dim3((unsigned)nb), dim3(256), 0, st, d2, n, p, out)
-  COV_DISPATCH(kernel_id, GEOBO_KE);
+  COV_DISPATCH_ALL(kernel_id, GEOBO_KE);
 #undef GEOBO_KE
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }

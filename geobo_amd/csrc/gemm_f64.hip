@@ -726,7 +726,7 @@ extern "C" int geobo_ak_fused(int kernel_id, const double* A, int64_t Ms_pad, in
   a.cov = make_cov(kernel_id, l1, l2, w, amp);
   hipStream_t st = (hipStream_t)stream;
 #define GEOBO_FUSED(ID) return launch_by_rows<Y_GEN, EPI_STORE, ID>(a, Ms_pad, ncols, st)
-  COV_DISPATCH(kernel_id, GEOBO_FUSED);
+  COV_DISPATCH_ALL(kernel_id, GEOBO_FUSED);
 #undef GEOBO_FUSED
   return GEOBO_E_ARG;
 }

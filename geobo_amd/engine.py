@@ -80,6 +80,49 @@ def weight_matrix(crossweights):
     return [[1.0, w3, w1], [w3, 1.0, w2], [w1, w2, 1.0]]
 
 
+class DirectionalCov:
+    """Covariance provider of the derivative of K along a direction d in the three lengths (PosteriorEngine.logl_grad).
+    Block (row property i, column property j) of create_cov is w_ij k(l1 = l_j, l2 = l_i), so its directional derivative is
+    w_ij (d_j dk/dl1 + d_i dk/dl2); a self block has one length: w d_j dk/dl.  The blocks (i, j) and (j, i) stay transposes of each
+    other (k_ij(a, b) = k_ji(b, a)), so the derivative Gram is symmetric and runs through every route of the assembly unchanged."""
+
+    def __init__(self, d):
+        self.d = [float(v) for v in d]
+
+    def terms(self, name, i, j, W):
+        w = W[i][j]
+        if i == j:
+            return [(hip.kernel_id(name, False, 1), w * self.d[j])]
+        return [(hip.kernel_id(name, True, 1), w * self.d[j]), (hip.kernel_id(name, True, 2), w * self.d[i])]
+
+    def table(self, eng, name, i, j, lengths, W, amp):
+        tabs = [eng._cov_table(kid, lengths[j], lengths[i], w, amp) for kid, w in self.terms(name, i, j, W)]
+        for t in tabs[1:]:
+            tabs[0].add_(t)
+        return tabs[0]
+
+    def k_block(self, eng, name, i, j, rows, cols, lengths, W, amp, out):
+        terms = self.terms(name, i, j, W)
+        hip.k_block(terms[0][0], rows, cols, lengths[j], lengths[i], terms[0][1], amp, out)
+        for kid, w in terms[1:]:
+            tmp = eng._workspace2d("dcov_tmp", out.shape[0], out.shape[1])
+            hip.k_block(kid, rows, cols, lengths[j], lengths[i], w, amp, tmp)
+            out.add_(tmp)
+        return out
+
+    def ak_fused(self, eng, name, s_, j, A, xyz, nc, lengths, W, amp, out):
+        terms = self.terms(name, s_, j, W)
+        hip.ak_fused(terms[0][0], A, xyz, eng.c0, nc, lengths[j], lengths[s_], terms[0][1], amp, out)
+        for kid, w in terms[1:]:
+            tmp = eng._workspace2d("dak_tmp", out.shape[0], nc)
+            hip.ak_fused(kid, A, xyz, eng.c0, nc, lengths[j], lengths[s_], w, amp, tmp)
+            out[:, :nc].add_(tmp)
+        return out
+
+
+# weight -> the block pair it multiplies (weight_matrix): w1 on (0, 2), w2 on (1, 2), w3 on (0, 1)
+WEIGHT_PAIRS = ((0, 2), (1, 2), (0, 1))
+
 _XGROUPS = {}
 
 
@@ -215,6 +258,12 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         # all-reduce and agreement go through the backend with one rank (sharding._live)
         self.force_collectives = os.environ.get("GEOBO_FORCE_COLLECTIVES", "0") == "1"
         self.kernel_events = None  # set to [] to record (name, flops, start, stop) HIP events per fused launch
+        # log-likelihood gradient (logl_grad): covariance provider of a derivative Gram (None: the covariance itself), workspace
+        # renames that keep its A K / Gram apart from the step's own, no noise diagonal, and the K copy a step leaves for it
+        self._dprov = None
+        self._ws_alias = None
+        self._grad_gram = False
+        self._keep_signal = False
         self.aka_hook = None       # callable(AkA) run between the assembly of AkA and its factorisation (emulation tool only)
 
     # ---- geometry --------------------------------------------------------------------------------------------
@@ -451,6 +500,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
 
     def _workspace(self, name, shape, dtype=F64):
         """Persistent uninitialised device tensor; reallocated only when the shape changes (large hipMallocs are slow)."""
+        if self._ws_alias:
+            name = self._ws_alias.get(name, name)
         t = self._ws.get(name)
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
             self._ws.pop(name, None)
@@ -508,6 +559,26 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         sset = self.s
         tab = hip.cov_table(kid, self.nx, self.ny, self.nz, sset.xvoxsize, sset.yvoxsize, sset.zvoxsize, lj, ls, w, amp, self.device)
         return hip.round_f32_(tab) if self.f32 else tab
+
+    def _block_table(self, name, i, j, lengths, W, amp):
+        """Lattice table of covariance block (row property i, column property j) = w_ij k2(l_j, l_i) (kernels.py:183-195), or, while a
+        derivative provider is set (logl_grad), the table of that block's derivative."""
+        if self._dprov is not None:
+            return self._dprov.table(self, name, i, j, lengths, W, amp)
+        return self._cov_table(hip.kernel_id(name, i != j), lengths[j], lengths[i], W[i][j], amp)
+
+    def _k_block(self, name, i, j, rows, cols, lengths, W, amp, out):
+        """Block (i, j) of create_cov evaluated from coordinates (geobo_k_block), through the derivative provider when one is set."""
+        if self._dprov is not None:
+            return self._dprov.k_block(self, name, i, j, rows, cols, lengths, W, amp, out)
+        return hip.k_block(hip.kernel_id(name, i != j), rows, cols, lengths[j], lengths[i], W[i][j], amp, out)
+
+    def _ak_fused_block(self, name, s_, j, A, xyz, nc, lengths, W, amp, out):
+        """A_s K_sj with the covariance generated inside the fused product (coordinate route), through the derivative provider when
+        one is set."""
+        if self._dprov is not None:
+            return self._dprov.ak_fused(self, name, s_, j, A, xyz, nc, lengths, W, amp, out)
+        return hip.ak_fused(hip.kernel_id(name, s_ != j), A, xyz, self.c0, nc, lengths[j], lengths[s_], W[s_][j], amp, out)
 
     @_on_device
     def apply_operator(self, A, v):
@@ -594,19 +665,18 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             for s_, A in ((0, A_g), (1, A_m)):
                 if self.use_spectral:
                     break
-                kid = hip.kernel_id(name, s_ != j)
                 # block (row-block s, col-block j) of create_cov is w * k2(l_j, l_s)  (kernels.py:183-195)
                 out = AK[s_ * self.Ms_pad:(s_ + 1) * self.Ms_pad, cols]
                 out64 = out if not self.f32 else self._workspace2d("ak_block64", self.Ms_pad, nc)
                 if self.use_grid:
                     # regular grid: covariance = table on the index-difference lattice (built once per block, N doubles)
-                    tab = self._cov_table(kid, lengths[j], lengths[s_], W[s_][j], amp)
+                    tab = self._block_table(name, s_, j, lengths, W, amp)
                     self._timed("ak_fused_grid", 2.0 * self.Ms_pad * self.N_pad * nc,
                                 lambda: hip.ak_fused_grid(A, self.nx, self.ny, self.nz, tab, self.c0, nc, out64),
                                 alg=2.0 * self.Ms * self.N * min(nc, max(self.N - self.c0, 0)))
                 else:
                     self._timed("ak_fused", 2.0 * self.Ms_pad * self.N_pad * nc,
-                                lambda: hip.ak_fused(kid, A, xyz, self.c0, nc, lengths[j], lengths[s_], W[s_][j], amp, out64),
+                                lambda: self._ak_fused_block(name, s_, j, A, xyz, nc, lengths, W, amp, out64),
                                 alg=2.0 * self.Ms * self.N * min(nc, max(self.N - self.c0, 0)))
                 if self.f32:
                     hip.convert(out64, out)
@@ -619,17 +689,16 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         int64 device tensor) and the voxel columns col0 .. col0 + out.shape[1]: materialised covariance assembly.  On the regular
         grid a gather from the block's difference-lattice table (geobo_k_block_grid: bound by the HBM store), otherwise evaluated
         from coordinates (geobo_k_block)."""
-        kid = hip.kernel_id(name, i != j)
         ncv = min(out.shape[1], max(self.N - col0, 0))       # columns behind N are voxel padding (zeroed by the caller)
         if ncv <= 0:
             return out
         if self.use_grid and col0 % 2 == 0:
-            tab = self._cov_table(kid, lengths[j], lengths[i], W[i][j], amp)
+            tab = self._block_table(name, i, j, lengths, W, amp)
             return hip.k_block_grid(tab, self.nx, self.ny, self.nz, rows_t, col0, out[:, :ncv])
         xyz = self.grid_points()
         rows = tuple(c[rows_t] for c in xyz)
         colc = tuple(c[col0:col0 + out.shape[1]] for c in xyz)
-        return hip.k_block(kid, rows, colc, lengths[j], lengths[i], W[i][j], amp, out)
+        return self._k_block(name, i, j, rows, colc, lengths, W, amp, out)
 
     def _assemble_AK_spectral(self, AK, A_g, A_m, lengths, W, name, amp, props, sym=False):
         """Sensor rows of AK through the real-DFT route (geobo_amd/spectral.py): same product, ~200x fewer flops."""
@@ -641,8 +710,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         for s_, A in ((0, A_g), (1, A_m)):
             lams, outs = [], []
             for jj, j in enumerate(props):
-                tab = self._cov_table(hip.kernel_id(name, s_ != j), lengths[j], lengths[s_], W[s_][j], amp)
-                gen = sp.eigenvalues(tab)
+                gen = sp.eigenvalues(self._block_table(name, s_, j, lengths, W, amp))
                 self._gens[(s_, j)] = gen               # (the transposed posterior path applies the same blocks to L^-1 A_s)
                 if sym and (s_, j) not in ((0, 0), (0, 1), (1, 1)):
                     continue
@@ -799,19 +867,28 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         return self._finish_AkA(AkA, M_pad, sel_t, lengths, name, amp, gp_sigma)
 
     def _finish_AkA(self, AkA, M_pad, sel_t, lengths, name, amp, gp_sigma):
-        """Drill columns by symmetry, the drill-drill block, the noise variances on the diagonal (identity on the padding)."""
+        """Drill columns by symmetry, the drill-drill block, the noise variances on the diagonal (identity on the padding).
+        A derivative Gram (logl_grad) gets neither: its padding stays zero.  _keep_signal: the matrix before the diagonal is copied
+        into the "K_signal" workspace (the signal part of K, for the amplitude and weight derivatives)."""
         xyz = self.grid_points()
         Md = 0 if sel_t is None else sel_t.numel()
         off_d = 2 * self.Ms_pad
-        dvec = torch.ones(M_pad, dtype=F64, device=self.device)
-        dvec[0:self.Ms] = float(gp_sigma[0]) ** 2
-        dvec[self.Ms_pad:self.Ms_pad + self.Ms] = float(gp_sigma[1]) ** 2
+        if not self._grad_gram:
+            dvec = torch.ones(M_pad, dtype=F64, device=self.device)
+            dvec[0:self.Ms] = float(gp_sigma[0]) ** 2
+            dvec[self.Ms_pad:self.Ms_pad + self.Ms] = float(gp_sigma[1]) ** 2
         if Md:
             AkA[:off_d, off_d:off_d + Md] = AkA[off_d:off_d + Md, :off_d].t()
             rows = tuple(c[sel_t] for c in xyz)
-            hip.k_block(hip.kernel_id(name, False), rows, rows, lengths[2], lengths[2], 1.0, amp,
-                        AkA[off_d:off_d + Md, off_d:off_d + Md])
-            dvec[off_d:off_d + Md] = float(gp_sigma[2]) ** 2
+            # (create_cov's self blocks carry weight 1; a derivative Gram's weight matrix may have 0 there: the unit-weight pair Gram)
+            W = self._W if self._grad_gram else [[1.0] * 3] * 3
+            self._k_block(name, 2, 2, rows, rows, lengths, W, amp, AkA[off_d:off_d + Md, off_d:off_d + Md])
+            if not self._grad_gram:
+                dvec[off_d:off_d + Md] = float(gp_sigma[2]) ** 2
+        if self._grad_gram:
+            return AkA
+        if self._keep_signal:
+            self._workspace("K_signal", tuple(AkA.shape)).copy_(AkA)
         AkA.diagonal().add_(dvec)
         return AkA
 
@@ -842,9 +919,20 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
 
     @_on_device
     def posterior(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp=1.0,
-                  props=(0, 1, 2), calclogl=True, want_mean_var=True):
+                  props=(0, 1, 2), calclogl=True, want_mean_var=True, keep_K=False):
         """Posterior mean / variance / log-likelihood.  `lengths` must already carry the create_cov mutation.
-        Returns dict(mu (3N, NaN for skipped property blocks), var, logl, info)."""
+        Returns dict(mu (3N, NaN for skipped property blocks), var, logl, info).
+        keep_K (internal, logl_grad): keep a copy of the assembled K without its diagonal (workspace "K_signal") before the
+        in-place factorisation."""
+        self._keep_signal = bool(keep_K)
+        try:
+            return self._posterior(A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, props, calclogl,
+                                   want_mean_var)
+        finally:
+            self._keep_signal = False
+
+    def _posterior(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, props, calclogl,
+                   want_mean_var):
         props = tuple(props)
         assert 0 in props and 1 in props, "gravity and magnetic blocks are needed for AkA"
         W = self._W = weight_matrix(crossweights)
@@ -958,6 +1046,76 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         whole = AK is not None and not self._ak_sym
         self.last = dict(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props, sel=sel)
         return out
+
+    def _derivative_gram(self, A_g, A_m, sel_t, lengths, W, name, amp, props, provider, slot):
+        """A derivative Gram dK in workspace `slot`: posterior()'s own assembly (_assemble_AK / _assemble_AkA, whichever route the
+        step takes) fed by `provider` (None: the covariance tables themselves, here with the weight matrix W), without the noise
+        diagonal, zero padding, lower triangle valid.  A K and the Gram go to workspaces of their own, and what a later step reads
+        of this one (the block generators, the plan flags) is restored."""
+        saved = (self._gens, self._W, getattr(self, "_ak_sym", False), self._rowpath, self._fullrows)
+        self._gens = dict(self._gens)
+        self._dprov, self._ws_alias, self._grad_gram = provider, {"AK": "dK_AK", "AkA": slot}, True
+        try:
+            AK, M_pad = self._assemble_AK(A_g, A_m, sel_t, lengths, W, name, amp, props,
+                                          sym=not self.rows_static and self._sym_ok(A_g, A_m))
+            return self._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, lengths, name, amp, None, props)
+        finally:
+            self._dprov, self._ws_alias, self._grad_gram = None, None, False
+            self._gens, self._W, self._ak_sym, self._rowpath, self._fullrows = saved
+
+    @_on_device
+    def logl_grad(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, directions):
+        """Exact gradient of f = (u.u + log det K) / 2 (calc_logl without the N log 2 pi term), K = amp sum_ij W_ij B_ij + D:
+            df/dtheta = <S, dK/dtheta> / 2,   S = K^-1 - alpha alpha^T,   alpha = L^-T u,   K^-1 = L^-T L^-1 (never stored).
+        One posterior() step (likelihood only) keeps K's signal part; G_0 = that part, plus the unit-weight blocks amp (B_ab + B_ba) of
+        any pair whose weight is 0 (its block of K is zero); G_t = the Gram of the directional derivative along directions[t - 1]
+        (`lengths` carry the create_cov mutation; directions are in the same metres).  One geobo_kinv_dot launch gives the block
+        sums of <S, G_t> per pair of row segments, from which
+            d_amp = sum over the non-zero-weight pairs / amp,  d_w = pair (a, b) / w (or the unit block's sum where w = 0),
+            d_dir[t] = all pairs of G_t,
+        each halved.  Returns dict(uu, logdet, d_amp, d_w (3,), d_dir (len(directions),)).  One rank, fp64 assembly."""
+        if self.world > 1:
+            raise ValueError("logl_grad runs on one rank (world = %d): the multi-rank gradient is not implemented" % self.world)
+        if self.f32:
+            raise ValueError("logl_grad needs the fp64 assembly (assembly='f32' keeps fp32 covariance tables)")
+        directions = [np.asarray(d, dtype=float).reshape(3) for d in directions]
+        if len(directions) > 3:
+            raise ValueError("at most three length directions per evaluation")
+        props = (0, 1, 2)
+        r = self.posterior(A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp=gp_amp, props=props,
+                           calclogl=True, want_mean_var=False, keep_K=True)
+        W = weight_matrix(crossweights)
+        Linv, u = self.last["Linv"], self.last["u"]
+        M_pad = Linv.shape[0]
+        sel = np.asarray(sel, dtype=np.int64)
+        sel_t = torch.as_tensor(sel, device=self.device) if sel.size else None
+        alpha = hip.colgemv(Linv, u, ws=self._workspace("grad_colgemv_ws", (hip.colgemv_ws_doubles(M_pad, M_pad),)))   # L^-T u
+        G0 = self._workspace("K_signal", (M_pad, M_pad))
+        wvals = [W[a][b] for a, b in WEIGHT_PAIRS]
+        if any(w == 0.0 for w in wvals):
+            Wu = [[0.0] * 3 for _ in range(3)]
+            for (a, b), w in zip(WEIGHT_PAIRS, wvals):
+                if w == 0.0:
+                    Wu[a][b] = Wu[b][a] = 1.0
+            G0.add_(self._derivative_gram(A_g, A_m, sel_t, lengths, Wu, kernelfunc, gp_amp, props, None, "dK_unit"))
+        Gs = [G0] + [self._derivative_gram(A_g, A_m, sel_t, lengths, W, kernelfunc, gp_amp, props, DirectionalCov(d), "dK_dir%d" % t)
+                     for t, d in enumerate(directions)]
+        segs = ((0, self.Ms), (self.Ms_pad, self.Ms_pad + self.Ms), (2 * self.Ms_pad, 2 * self.Ms_pad + len(sel)))
+        out = self._timed("kinv_dot", M_pad ** 3 / 3.0, lambda: hip.kinv_dot(
+            Linv, alpha, Gs, segs, ws=self._workspace("kinv_dot_ws", (hip.kinv_dot_ws_doubles(M_pad, len(Gs)),))))
+        o = self._to_host(out, "kinv_dot").reshape(len(Gs), 3, 3).copy()
+        pair = lambda t, a, b: float(o[t, a, b])
+        diag = sum(pair(0, a, a) for a in range(3))
+        d_w = np.empty(3)
+        off = 0.0
+        for k, ((a, b), w) in enumerate(zip(WEIGHT_PAIRS, wvals)):
+            if w == 0.0:
+                d_w[k] = 0.5 * pair(0, a, b)
+            else:
+                d_w[k] = 0.5 * pair(0, a, b) / w
+                off += pair(0, a, b)
+        d_dir = np.array([0.5 * sum(pair(t, a, b) for a in range(3) for b in range(a, 3)) for t in range(1, len(Gs))])
+        return dict(uu=r["uu"], logdet=r["logdet"], d_amp=0.5 * (diag + off) / gp_amp, d_w=d_w, d_dir=d_dir)
 
     @_on_device
     def posterior_covariance(self, kernelfunc, lengths, crossweights, gp_amp=1.0, limit_bytes=48 << 30):

@@ -13,17 +13,29 @@ from . import _lib
 
 F64 = torch.float64
 
-KERNEL_IDS = {"d2": 0, "exp": 1, "exp_x": 2, "matern32": 3, "matern32_x": 4, "sparse": 5, "sparse_x": 6}
+KERNEL_IDS = {"d2": 0, "exp": 1, "exp_x": 2, "matern32": 3, "matern32_x": 4, "sparse": 5, "sparse_x": 6,
+              # partial derivatives in the lengths (log-likelihood gradient): self families d/dl, cross families d/dl1, d/dl2
+              "exp_dl": 7, "exp_x_dl1": 8, "exp_x_dl2": 9, "matern32_dl": 10, "matern32_x_dl1": 11, "matern32_x_dl2": 12,
+              "sparse_dl": 13, "sparse_x_dl1": 14, "sparse_x_dl2": 15}
 FUNC_IDS = {"grav": 0, "magn": 1}
 # kernel-instance tables and padding units: ONE definition (plan.py, which decides routes from them on the CPU); re-exported here
 from .plan import PAD_M, PAD_N, SPECTRAL_AXIS_N, SPECTRAL_Y_NY, TOEPLITZ_NY, XZ2D_FOLD_N, XZ2D_SHAPES  # noqa: E402,F401
 
 
-def kernel_id(name, cross):
-    """(kernelfunc, is-cross-block) -> family id of include/geobo_hip.h (kernels.py:183-195)."""
+def kernel_id(name, cross, deriv=None):
+    """(kernelfunc, is-cross-block) -> family id of include/geobo_hip.h (kernels.py:183-195).
+    deriv: None = the covariance itself; 1 / 2 = its partial derivative in l1 / l2 (the self families have one length: deriv 1)."""
     if name not in ("exp", "matern32", "sparse"):
         raise ValueError("unknown kernelfunc %r (expected 'sparse', 'exp' or 'matern32')" % (name,))
-    return KERNEL_IDS[name + ("_x" if cross else "")]
+    if deriv is None:
+        return KERNEL_IDS[name + ("_x" if cross else "")]
+    if isinstance(deriv, bool) or deriv not in (1, 2):
+        raise ValueError("deriv must be None, 1 or 2, got %r" % (deriv,))
+    if not cross:
+        if deriv != 1:
+            raise ValueError("the self family %r has one length: deriv must be 1" % (name,))
+        return KERNEL_IDS[name + "_dl"]
+    return KERNEL_IDS["%s_x_dl%d" % (name, deriv)]
 
 
 def pad_m(m):
@@ -748,6 +760,37 @@ def posterior_reduce(Linv, AK, u, prior_var, ws=None, m_valid=0):
                                           _stream()),
                "geobo_posterior_reduce")
     return mu, var
+
+
+def kinv_dot_ws_doubles(m, T):
+    return max(_lib.load().geobo_kinv_dot_ws_bytes(int(m), int(T)) // 8, 1)
+
+
+def kinv_dot(Linv, alpha, Gs, segs, ws=None, out=None):
+    """out[t, a, b] = sum over rows i of segment a, columns j of segment b of (Linv^T Linv - alpha alpha^T)_ij Gs[t]_ij, Gs[t] given
+    by its lower triangle (symmetric); segs: three (start, end) row ranges, starts multiples of 256.  K^-1 is never stored."""
+    lib = require_gpu()
+    m = Linv.shape[0]
+    ldl = _rowmajor(Linv, "Linv")
+    T = len(Gs)
+    if not 1 <= T <= 4:
+        raise ValueError("kinv_dot takes 1 to 4 matrices, got %d" % T)
+    ldg = _rowmajor(Gs[0], "G")
+    for g in Gs:
+        if _rowmajor(g, "G") != ldg or tuple(g.shape) != (m, m):
+            raise ValueError("every G must be (m x m) with the same leading dimension")
+    alpha = _chk(alpha, "alpha")
+    assert alpha.is_contiguous() and alpha.numel() >= m and Linv.shape[1] == m
+    seg = (C.c_int64 * 6)(*[int(v) for ab in segs for v in ab])
+    gp = (C.c_void_p * T)(*[g.data_ptr() for g in Gs])
+    if out is None:
+        out = torch.empty((T, 3, 3), dtype=F64, device=Linv.device)
+    nbytes = lib.geobo_kinv_dot_ws_bytes(m, T)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty(max(nbytes // 8, 1), dtype=F64, device=Linv.device)
+    _lib.check(lib.geobo_kinv_dot(m, _p(Linv), ldl, _p(alpha), T, gp, ldg, seg, _p(_chk(out, "out")), _p(ws), nbytes, _stream()),
+               "geobo_kinv_dot")
+    return out
 
 
 def mfma_f64_peak(blocks=1024, iters=20000):

@@ -59,6 +59,11 @@ class DiagonalCovariance:
                         ".diagonal(), or predict3(full_cov=True) on a cube small enough to hold (3N)^2 doubles")
 
 
+def reference_length_direction(xvoxsize):
+    """d lengths / d l of calc_logl's single length scale: l xvox (1, 1, 1) becomes l xvox (1, 1.02, 1) in create_cov."""
+    return xvoxsize * np.array([1.0, 1.02, 1.0])
+
+
 def _zscore(v):
     """(v - mean) / std with the population std, and that std (inversion.py:209-214); NaN for an empty vector."""
     with np.errstate(all="ignore"):
@@ -118,14 +123,19 @@ class Inversion:
         # inversion.py:219 + sensormodel.A_drill: rows = voxels with non-zero drill data, ascending flat index
         return np.flatnonzero(np.asarray(self.drilldata0).reshape(-1) != 0)
 
-    def _run(self, gp_amp, gp_length, coeffm, calclogl, want_mean_var):
+    def _run(self, gp_amp, gp_length, coeffm, calclogl, want_mean_var, directions=None):
+        """One step of the engine: posterior(), or with `directions` (lists of three length components, metres) the likelihood
+        and its exact gradient (PosteriorEngine.logl_grad)."""
         A_g, A_m = self._operators()
         lengths = create_cov_lengths(gp_length)  # in-place edit of the caller's array, like create_cov
         ng, nm = self.gravfield.size, self.magfield.size
-        step = lambda: self.engine.posterior(A_g, A_m, self._sel, self.Fs3[:ng], self.Fs3[ng:ng + nm], self.Fs3[ng + nm:],
-                                             [float(v) for v in lengths], self.coeffm if coeffm is None else coeffm,
-                                             self.settings.kernelfunc, self.gp_sigma, gp_amp=gp_amp, props=self.props,
-                                             calclogl=calclogl, want_mean_var=want_mean_var)
+        args = (A_g, A_m, self._sel, self.Fs3[:ng], self.Fs3[ng:ng + nm], self.Fs3[ng + nm:], [float(v) for v in lengths],
+                self.coeffm if coeffm is None else coeffm, self.settings.kernelfunc, self.gp_sigma)
+        if directions is None:
+            step = lambda: self.engine.posterior(*args, gp_amp=gp_amp, props=self.props, calclogl=calclogl,
+                                                 want_mean_var=want_mean_var)
+        else:
+            step = lambda: self.engine.logl_grad(*args, gp_amp, directions)
         try:
             return step()
         except FactorisationTimeout:
@@ -182,6 +192,40 @@ class Inversion:
             logl = -np.inf
         return -logl
 
+    def calc_logl_grad(self, params):
+        """calc_logl(params) and its exact gradient in the same 5 parameters (amplitude, lengthscale in x-voxels, w1, w2, w3).
+        The value comes from the same step as calc_logl's and equals it bit for bit; the gradient is <K^-1 - alpha alpha^T, dK>/2
+        on the device (PosteriorEngine.logl_grad).  The lengths after create_cov's mutation are l xvox (1, 1.02, 1), so d/dl is ONE
+        directional derivative along xvox (1, 1.02, 1).  Failure (as calc_logl's inf): (inf, NaN * ones(5))."""
+        s = self.settings
+        gp_amp = params[0]
+        gp_length = params[1] * np.asarray([s.xvoxsize, s.xvoxsize, s.xvoxsize])
+        coeffm = params[2:]
+        try:
+            r = self._run(gp_amp, gp_length, coeffm, True, False, directions=[reference_length_direction(s.xvoxsize)])
+            logl = -0.5 * (r["uu"] + r["logdet"])
+            grad = np.r_[r["d_amp"], r["d_dir"][0], r["d_w"]]
+            if not np.isfinite(logl) or not np.isfinite(grad).all():
+                raise FloatingPointError
+        except Exception:
+            return np.inf, np.full(5, np.nan)
+        return -logl, grad
+
+    def neg_logl_and_grad(self, gp_amp, gp_length, coeffm):
+        """Negative log marginal likelihood (calc_logl's objective) and its gradient in the 7 parameters (amplitude, l0, l1, l2, w1, w2,
+        w3) with three free length scales in metres, taken after create_cov's mutation (applied to a copy: gp_length is not edited).
+        Three directional derivatives, one per length.  Failure: (inf, NaN * ones(7))."""
+        lengths = np.array(gp_length, dtype=float).reshape(3)
+        try:
+            r = self._run(float(gp_amp), lengths, np.asarray(coeffm, dtype=float), True, False, directions=list(np.eye(3)))
+            logl = -0.5 * (r["uu"] + r["logdet"])
+            grad = np.r_[r["d_amp"], r["d_dir"], r["d_w"]]
+            if not np.isfinite(logl) or not np.isfinite(grad).all():
+                raise FloatingPointError
+        except Exception:
+            return np.inf, np.full(7, np.nan)
+        return -logl, grad
+
     # ---- inversion.py:155-178 ---------------------------------------------------------------------------------------
     def hyper_bounds(self):
         """Search box of optimize_gp: amplitude, lengthscale (in x-voxels) and the three cross-correlation weights."""
@@ -200,11 +244,27 @@ class Inversion:
         self.coeffm = x[2:5].copy()
 
     def optimize_gp(self):
-        """Maximise the marginal likelihood over the box of hyper_bounds() with SciPy's SHGO (10 Sobol points x 10
-        iterations, as the reference); every objective evaluation is one AkA + Cholesky + log-det on the device."""
-        from scipy.optimize import shgo
+        """Maximise the marginal likelihood over the box of hyper_bounds() (the reference's entry point and signature): SHGO as the
+        reference, or L-BFGS-B on the exact gradient where the settings carry optimize_method: "L-BFGS-B" (optional YAML key,
+        default "shgo").  See optimize_hyperparameters."""
+        return self.optimize_hyperparameters(method=getattr(self.settings, "optimize_method", "shgo"))
+
+    def optimize_hyperparameters(self, method="shgo", free_lengths=False):
+        """Maximise the marginal likelihood over the box of hyper_bounds().
+        method "shgo" (default): SciPy's SHGO (10 Sobol points x 10 iterations, as the reference); every objective evaluation is one
+        AkA + Cholesky + log-det on the device.
+        method "L-BFGS-B": scipy.optimize.minimize with the exact gradient (calc_logl_grad), from the current parameters.
+        free_lengths (L-BFGS-B only): the 7 parameters of neg_logl_and_grad -- three free length scales, each in the reference's length
+        box -- which makes Matern-3/2 fittable; the result is stored in gp_length as three lengths."""
         print("Optimizing GP hyperparameters and correlation coefficients, this may take a while...")
         self.datastd = np.mean([np.nanstd(v) for v in (self.gravfield, self.magfield, self.drillfield)])
+        if method == "L-BFGS-B":
+            return self._optimize_lbfgsb(free_lengths)
+        if method != "shgo":
+            raise ValueError("optimize_hyperparameters: method must be 'shgo' or 'L-BFGS-B', got %r" % (method,))
+        if free_lengths:
+            raise ValueError("free_lengths needs method='L-BFGS-B'")
+        from scipy.optimize import shgo
         found = shgo(self.calc_logl, bounds=self.hyper_bounds(), n=10, iters=10, sampling_method="sobol")
         if not found.success:
             print("WARNING: " + found.message)     # parameters stay as they were
@@ -213,6 +273,41 @@ class Inversion:
         report("Initial parameter [amplitude, lengthscale, corr1, corr2, corr3]:")
         self.set_hyperparameters(found.x)
         report("Optimized parameter [amplitude, lengthscale, corr1, corr2, corr3]:")
+        return found
+
+    def _optimize_lbfgsb(self, free_lengths):
+        """optimize_hyperparameters(method="L-BFGS-B"): bounded quasi-Newton on the exact gradient.  Lengths are optimised in x-voxel
+        units (the 7-vector's gradient is scaled accordingly), which keeps the problem as well scaled as the reference's 5-vector."""
+        from scipy.optimize import minimize
+        s = self.settings
+        xv = s.xvoxsize
+        box = self.hyper_bounds()
+        if free_lengths:
+            bounds = [box[0]] + [box[1]] * 3 + list(box[2:])
+            x0 = np.r_[self.gp_amp, np.asarray(self.gp_length, dtype=float) / xv, self.coeffm]
+
+            def fun(x):
+                f, g = self.neg_logl_and_grad(x[0], x[1:4] * xv, x[4:7])
+                return f, np.r_[g[0], g[1:4] * xv, g[4:7]]
+        else:
+            bounds = list(box)
+            x0 = np.r_[self.gp_amp, float(np.asarray(self.gp_length, dtype=float)[0]) / xv, self.coeffm]
+            fun = self.calc_logl_grad
+        x0 = np.clip(np.asarray(x0, dtype=float), [b[0] for b in bounds], [b[1] for b in bounds])
+        found = minimize(fun, x0, jac=True, method="L-BFGS-B", bounds=bounds)
+        if not found.success:
+            print("WARNING: " + str(found.message))     # parameters stay as they were
+            return found
+        report = lambda title: print(title + "\n" + " ".join(str(v) for v in (self.gp_amp, self.gp_length, self.coeffm)))
+        if free_lengths:
+            report("Initial parameter [amplitude, lengthscale, corr1, corr2, corr3]:")
+            x = np.asarray(found.x, dtype=float)
+            self.gp_amp, self.gp_length, self.coeffm = x[0], x[1:4] * xv, x[4:7].copy()
+            report("Optimized parameter [amplitude, lengthscale, corr1, corr2, corr3]:")
+        else:
+            report("Initial parameter [amplitude, lengthscale, corr1, corr2, corr3]:")
+            self.set_hyperparameters(found.x)
+            report("Optimized parameter [amplitude, lengthscale, corr1, corr2, corr3]:")
         return found
 
     # ---- inversion.py:182-248 ---------------------------------------------------------------------------------------
@@ -242,7 +337,7 @@ class Inversion:
             raise ValueError("drillfield must hold one value per non-zero voxel of drilldata0")
         self.Fs3 = np.hstack((gravfield_norm, magfield_norm, drillfield_norm))
         if s.optimize_gp:
-            self.optimize_gp()
+            self.optimize_gp()     # (optional YAML key optimize_method: "shgo", the default, or "L-BFGS-B")
         self.mu_rec, self.cov_rec, self.logl = self.predict3(calclogl=True)
         shape = (3, s.yNcube, s.xNcube, s.zNcube)
         mean_cubes = self.mu_rec.reshape(shape)

@@ -101,7 +101,7 @@ class RowFormMixin:
                                 lambda: self._rows_times_AT(pre[(s_, j)][:, :self.N], rows_r, j, loc[:, k * Msp:(k + 1) * Msp]))
                 continue
             for j in props:
-                gen = sp.eigenvalues(self._cov_table(hip.kernel_id(name, s_ != j), lengths[j], lengths[s_], W[s_][j], amp))
+                gen = sp.eigenvalues(self._block_table(name, s_, j, lengths, W, amp))
                 self._gens[(s_, j)] = gen            # (the transposed posterior applies the same blocks to L^-1 A_s)
             lams = [self._gens[(s_, j)] for j, _ in blocks]
             for c0 in range(0, rows_r, ck):

@@ -36,6 +36,10 @@ extern "C" {
 
 #define GEOBO_VERSION 212 /* 201: flag word of geobo_gemm_nt, (64, 32) instance of geobo_xz2d, workspace layout of geobo_potrf_inv; 202: geobo_ymul, geobo_xz2d_fold_lattice; 203: geobo_sumsq_accum, geobo_lamdot_z, geobo_toeplitz_y2t, geobo_xz2d_fold_quad; 204: geobo_toeplitz_y3_add; 205: workspace layout of geobo_potrf_inv (one T buffer per tree node); 206: geobo_potrf_inv as one persistent tile-DAG launch from m = 1024 (workspace: + counters); 207: geobo_gemm_fold; 208: geobo_gemm_fold_lamdot; 209: geobo_toeplitz_y2s; 210: geobo_xz2d_fold* dense planes take the quarter-period group order of the basis (radix 4); 211: geobo_ymul_fold; 212: geobo_spectral_y, geobo_spectral_y2s, geobo_spectral_y_basis, geobo_spectral_y3, geobo_spectral_y3t, geobo_spectral_axis, geobo_rowgemv */
 
+/* Additive since 212, version unchanged: covariance ids 7-15 (partial derivatives in the lengths, accepted by geobo_k_block,
+ * geobo_k_block_f32, geobo_k_eval, geobo_cov_table and geobo_ak_fused), geobo_kinv_dot and geobo_kinv_dot_ws_bytes.  No existing
+ * entry point, id or layout changed. */
+
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
 
@@ -109,7 +113,11 @@ int geobo_convert(int to_f32, const void* src, int64_t ld_src, void* dst, int64_
 int geobo_round_f32(double* x, int64_t n, void* stream);
 
 /* out[i] = w * amp * k(d2[i]; l1, l2), elementwise on a caller-supplied squared-distance array
- * (the literal signature of kernels.py:81-156: gpkernel(D2, gamma) ...). */
+ * (the literal signature of kernels.py:81-156: gpkernel(D2, gamma) ...).
+ * kernel_id: 0 d2, 1 exp, 2 exp_x, 3 matern32, 4 matern32_x, 5 sparse, 6 sparse_x; partial derivatives in the lengths
+ * (log-likelihood gradient; same ids in every covariance entry point): 7 d exp/dl, 8 / 9 d exp_x/dl1 / dl2, 10 d matern32/dl,
+ * 11 / 12 d matern32_x/dl1 / dl2, 13 d sparse/dl, 14 / 15 d sparse_x/dl1 / dl2 (where the reference clamps to 0 the derivative
+ * is 0; sparse_x's equal-length offset l2 -> 1.001 l2 is differentiated as a fixed factor). */
 int geobo_k_eval(int kernel_id, const double* d2, int64_t n, double l1, double l2, double w, double amp,
                  double* out, void* stream);
 
@@ -498,6 +506,20 @@ size_t geobo_posterior_ws_bytes(int64_t m, int64_t ncols);
 int geobo_posterior_reduce(int64_t m, int64_t ncols, const double* Linv, int64_t ldi, const double* AK, int64_t ldak,
                            const double* u, double prior_var, double* mu, double* var, int64_t m_valid, void* ws,
                            size_t ws_bytes, void* stream);
+
+/* Exact gradient of the negative log marginal likelihood f = (u.u + log det K) / 2:  df/dtheta = <S, dK/dtheta> / 2 with
+ * S = K^-1 - alpha alpha^T, K^-1 = Linv^T Linv, alpha = Linv^T u.  For T (1..4) symmetric matrices G_t, each given by its LOWER
+ * triangle only (m x m, leading dimension ldg, the upper triangle is never read):
+ *     out[t*9 + a*3 + b] = sum_{i in seg a, j in seg b} S_ij G_t[i][j]        (a != b: both halves, out symmetric in a, b)
+ * seg (HOST array of 6): half-open row ranges [seg[2a], seg[2a+1]) of the grav / magn / drill rows, ordered, each starting at a
+ * multiple of 256 (empty ranges allowed); rows outside them are not summed.  G: HOST array of T device pointers.  K^-1 is never
+ * stored: its lower 128 x 128 tiles are TN products of Linv rows on the fp64 MFMA, reduced against the G_t tiles in the epilogue;
+ * per-tile partial sums in ws (geobo_kinv_dot_ws_bytes(m, T)), added in a fixed order: bitwise reproducible, no atomics.
+ * Linv: lower triangular (the upper triangle is not read), m % 256 == 0, 16-byte aligned, ldl even.  Every argument check comes
+ * before any device access (GEOBO_E_ARG).  geobo_kinv_dot_ws_bytes returns 0 for invalid (m, T). */
+size_t geobo_kinv_dot_ws_bytes(int64_t m, int T);
+int geobo_kinv_dot(int64_t m, const double* Linv, int64_t ldl, const double* alpha, int T, const double* const* G, int64_t ldg,
+                   const int64_t* seg, double* out, void* ws, size_t ws_bytes, void* stream);
 
 /* u = Linv * y (lower-triangular mat-vec, wavefront shuffle reduction); also
  * stats[0] = u.u, stats[1] = sum_i log(L_ii^2)   (inversion.py:105-110).  Ldiag = L (m x m, ld). */
