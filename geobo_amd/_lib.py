@@ -82,6 +82,14 @@ SIGNATURES = {
     "geobo_posterior_reduce": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _dp, _f64, _dp, _dp, _i64, _dp, _sz, _dp]),
     "geobo_kinv_dot_ws_bytes": (_sz, [_i64, _int]),
     "geobo_kinv_dot": (_int, [_i64, _dp, _i64, _dp, _int, C.POINTER(_dp), _i64, C.POINTER(_i64), _dp, _dp, _sz, _dp]),
+    "geobo_philox_fill": (_int, [_int, C.c_uint64, C.c_uint64, _i64, _i64, _i64, _i64, C.c_uint64, _dp, _dp]),
+    "geobo_torus_table": (_int, [_int, _int, _int, _int, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _dp, _dp]),
+    "geobo_fft_lines": (_int, [_int, _i64]),
+    "geobo_fft_axis": (_int, [_int, _i64, _int, _i64, _int, _int, _dp, _dp, _int, _i64, _i64, _dp]),
+    "geobo_sample_factor_ws_bytes": (_sz, []),
+    "geobo_sample_factor": (_int, [_int, _int, _int, _int, _dp, _dp, _dp, _dp, _sz, _dp, _dp]),
+    "geobo_sample_zpass": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _dp, _dp, C.c_uint64, _dp, _dp]),
+    "geobo_spectral_mix": (_int, [_int, _i64, _int, _int, _int, _dp, _f64, _dp, _dp, _dp]),
     "geobo_trmv_stats": (_int, [_i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _dp]),
     "geobo_mfma_f64_peak": (_int, [_int, _int, _dp, _dp]),
     "geobo_mfma_mix": (_int, [_int, _int, _int, _int, _dp, _dp]),

@@ -1148,3 +1148,70 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         hip.gemm_nt(Vt, Vt, C, alpha=-1.0, beta=1.0)
         idx = torch.cat([torch.arange(self.N, device=self.device) + j * self.N_pad for j in range(3)])
         return C[idx][:, idx].cpu().numpy()
+
+    # ---- posterior realisations (Matheron's rule) ------------------------------------------------------------
+    def _operator_rows(self, A):
+        """(r0, rows) batches of a forward operator: the resident matrix at once, a streamed one 256 zero-padded rows at a time."""
+        if not isinstance(A, StreamedOperator):
+            yield 0, A[:self.Ms_pad, :self.N_pad]
+            return
+        buf = self._workspace2d("cond_op_rows", 256, self.N_pad)
+        for r0 in range(0, self.Ms, 256):
+            R = min(256, self.Ms - r0)
+            A.rows_into(buf, r0, R)
+            if R < 256:
+                buf[R:].zero_()
+            yield r0, buf
+
+    @_on_device
+    def condition(self, F, eps, A_g, A_m, y_g, y_m, y_d, sampler):
+        """Condition S prior samples on the data with the factor of the last posterior() step (Matheron's rule):
+            f_post = f + K A3^T w,   w = H^-1 (y - A3 f - eps) = L^-T L^-1 r,   H = A3 K A3^T + Sigma.
+        F: (S, 3, N) device prior samples (sampler.sample); eps: (S, M) device observation noise, rows [grav | magn | drill] unpadded.
+        A3 F and A3^T W are MFMA GEMMs against the operator (row batches of 256 for a streamed one); K (A3^T W) is the sampler's exact
+        circulant product, the same on every single-rank route.  Returns (f_post (S, 3, N), w (S, M))."""
+        if self.world > 1:
+            raise NotImplementedError("posterior sampling runs on one rank (world = %d)" % self.world)
+        last = self.last
+        if last is None or tuple(last["props"]) != (0, 1, 2):
+            raise RuntimeError("condition() needs the factor of a posterior() step over all three property blocks")
+        Linv = last["Linv"]
+        sel = np.asarray(last["sel"], dtype=np.int64)
+        M_pad, Ms, Msp, N, Np, Md = Linv.shape[0], self.Ms, self.Ms_pad, self.N, self.N_pad, len(sel)
+        off_d = 2 * Msp
+        S = F.shape[0]
+        Sp = hip.pad_m(S)
+        dev = self.device
+        # residual r = y - A3 f - eps, one padded row per sample
+        Rt = torch.zeros((Sp, M_pad), dtype=F64, device=dev)
+        Fp = torch.zeros((Sp, Np), dtype=F64, device=dev)
+        AF = torch.empty((Sp, Msp), dtype=F64, device=dev)
+        for j, (A, r0) in enumerate(((A_g, 0), (A_m, Msp))):
+            Fp[:S, :N] = F[:, j, :]
+            for c0, rows in self._operator_rows(A):
+                hip.gemm_nt(Fp, rows, AF[:, c0:c0 + rows.shape[0]])
+            Rt[:S, r0:r0 + Ms] = -AF[:S, :Ms]
+        Rt[:S, 0:Ms] += hip.to_dev(np.asarray(y_g, dtype=np.float64), dev)
+        Rt[:S, Msp:Msp + Ms] += hip.to_dev(np.asarray(y_m, dtype=np.float64), dev)
+        Rt[:S, 0:Ms] -= eps[:, 0:Ms]
+        Rt[:S, Msp:Msp + Ms] -= eps[:, Ms:2 * Ms]
+        if Md:
+            sel_t = torch.as_tensor(sel, device=dev)
+            Rt[:S, off_d:off_d + Md] = hip.to_dev(np.asarray(y_d, dtype=np.float64), dev) - F[:, 2, :][:, sel_t] - eps[:, 2 * Ms:2 * Ms + Md]
+        # w = L^-T (L^-1 r): rows of Z^T = R^T L^-T, then W^T = Z^T L^-1 (L^-1 lower triangular, upper part zero)
+        Zt = hip.gemm_nt(Rt, Linv, torch.empty((Sp, M_pad), dtype=F64, device=dev))
+        Wt = hip.gemm_nn(Zt, Linv, Rt, y_lower=True)
+        del Zt
+        # A3^T w on the voxel grid, block by block, then K through the circulant spectra
+        V = torch.zeros((S, 3, N), dtype=F64, device=dev)
+        Vp = torch.empty((Sp, Np), dtype=F64, device=dev)
+        for j, (A, r0) in enumerate(((A_g, 0), (A_m, Msp))):
+            for c0, rows in self._operator_rows(A):
+                hip.gemm_nn(Wt[:, r0 + c0:r0 + c0 + rows.shape[0]], rows, Vp, beta=1.0 if c0 else 0.0)
+            V[:, j, :] = Vp[:S, :N]
+        if Md:
+            V[:, 2, :][:, sel_t] = Wt[:S, off_d:off_d + Md]
+        f_post = sampler.apply_K(V)
+        f_post.add_(F)
+        w = torch.cat([Wt[:S, 0:Ms], Wt[:S, Msp:Msp + Ms], Wt[:S, off_d:off_d + Md]], dim=1)
+        return f_post, w

@@ -811,3 +811,75 @@ def mfma_f64_peak(blocks=1024, iters=20000):
 def to_dev(a, device="cuda"):
     require_gpu()
     return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), dtype=F64).to(device)
+
+
+# ---- prior sampler by circulant embedding (sampling.hip) ----------------------------------------------------------------------
+RNG_PRIOR, RNG_OBS = 0, 1
+FFT_INVERSE, FFT_IN_PAIRS, FFT_OUT_PAIRS, FFT_MAX = 1, 2, 4, 512
+
+
+def philox_fill(seed, purpose, sample0, nsamples, elem0, nelem, sub=0, raw=False, out=None, device="cuda"):
+    """(nsamples, nelem, 4) Philox4x64-10 blocks of counters (elem0 + e, sample0 + s, purpose, sub), key (seed, 0): raw 64-bit words
+    (int64 tensor holding the uint64 bits) or fp64 Box-Muller normals."""
+    lib = require_gpu()
+    if out is None:
+        out = torch.empty((int(nsamples), int(nelem), 4), dtype=torch.int64 if raw else F64, device=device)
+    _lib.check(lib.geobo_philox_fill(1 if raw else 0, int(seed), int(purpose), int(sample0), int(nsamples), int(elem0), int(nelem), int(sub),
+                                     _p(out), _stream()), "geobo_philox_fill")
+    return out
+
+
+def torus_table(kid, my, mx, mz, sx, sy, sz, l1, l2, w, amp, out):
+    """out (my*mx*mz*2 fp64, complex interleaved) = w amp k at the wrapped lags of the (my, mx, mz) torus."""
+    lib = require_gpu()
+    assert out.numel() >= 2 * my * mx * mz
+    _lib.check(lib.geobo_torus_table(int(kid), int(my), int(mx), int(mz), float(sx), float(sy), float(sz), float(l1), float(l2), float(w),
+                                     float(amp), _p(_chk(out, "out")), _stream()), "geobo_torus_table")
+    return out
+
+
+def fft_axis(flags, b0, m, b1, n_in, n_out, src, out, P=0, Q=0, S=0):
+    """Batched complex FFT along the middle axis of [b0][len][b1] (geobo_fft_axis).  Extents are checked against both allocations here."""
+    lib = require_gpu()
+    pairs_in, pairs_out = flags & FFT_IN_PAIRS, flags & FFT_OUT_PAIRS
+    need_in = (S * P * Q) if pairs_in else 2 * b0 * n_in * b1
+    need_out = (S * P * Q) if pairs_out else 2 * b0 * n_out * b1
+    if pairs_in or pairs_out:
+        assert (b0 * (n_in if pairs_in else n_out) * b1) == ((S + 1) // 2) * P * Q, "pair packing: extents do not match (S, P, Q)"
+    if src.numel() < need_in or out.numel() < need_out:
+        raise ValueError("geobo_fft_axis: operand smaller than its extents")
+    _lib.check(lib.geobo_fft_axis(int(flags), int(b0), int(m), int(b1), int(n_in), int(n_out), _p(_chk(src, "src")), _p(_chk(out, "out")),
+                                  int(P), int(Q), int(S), _stream()), "geobo_fft_axis")
+    return out
+
+
+def sample_factor(P, my, mx, mz, spectra, F, lam, ws, status):
+    lib = require_gpu()
+    no = (my // 2 + 1) * (mx // 2 + 1) * (mz // 2 + 1)
+    assert spectra.numel() >= P * (P + 1) * my * mx * mz and F.numel() >= no * P * P and lam.numel() >= no * P * (P + 1) // 2
+    _lib.check(lib.geobo_sample_factor(int(P), int(my), int(mx), int(mz), _p(_chk(spectra, "spectra")), _p(_chk(F, "F")), _p(_chk(lam, "lam")),
+                                       _p(ws), ws.numel() * ws.element_size(), _p(_chk(status, "status")), _stream()), "geobo_sample_factor")
+    return status
+
+
+def sample_factor_ws_doubles():
+    return int(_lib.load().geobo_sample_factor_ws_bytes()) // 8
+
+
+def sample_zpass(P, pair0, npairs, my, mx, mz, nz, F, out, seed=0, noise=None):
+    """Noise -> F / sqrt(M) -> inverse z FFT, cropped: out (npairs * P * my * mx * nz complex)."""
+    lib = require_gpu()
+    assert out.numel() >= 2 * npairs * P * my * mx * nz
+    if noise is not None:
+        assert _chk(noise, "noise").numel() >= 2 * npairs * my * mx * mz * P
+    _lib.check(lib.geobo_sample_zpass(int(P), int(pair0), int(npairs), int(my), int(mx), int(mz), int(nz), _p(_chk(F, "F")),
+                                      _p(noise) if noise is not None else None, int(seed), _p(_chk(out, "out")), _stream()), "geobo_sample_zpass")
+    return out
+
+
+def spectral_mix(P, npairs, my, mx, mz, lam, scale, src, out):
+    lib = require_gpu()
+    assert src.numel() >= 2 * npairs * P * my * mx * mz and out.numel() >= 2 * npairs * P * my * mx * mz
+    _lib.check(lib.geobo_spectral_mix(int(P), int(npairs), int(my), int(mx), int(mz), _p(_chk(lam, "lam")), float(scale), _p(_chk(src, "src")),
+                                      _p(_chk(out, "out")), _stream()), "geobo_spectral_mix")
+    return out

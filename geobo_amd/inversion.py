@@ -20,11 +20,13 @@ posterior diagonal that `cubing` consumes (inversion.py:238).  No CPU fallback e
 import sys
 
 import numpy as np
+import torch
 
 from . import config_loader, geometry
 from . import kernels as kernel
 from . import sensormodel as sm
-from .engine import CholeskyError, FactorisationTimeout, PosteriorEngine, create_cov_lengths
+from .engine import CholeskyError, FactorisationTimeout, PosteriorEngine, create_cov_lengths, weight_matrix
+from .sampling import PriorSampler, SamplingError, observation_noise  # noqa: F401  (SamplingError: public)
 
 
 class DiagonalCovariance:
@@ -71,6 +73,10 @@ def _zscore(v):
             return v - np.nan, np.nan
         std = v.std()
         return (v - v.mean()) / std, std
+
+
+def _hyper_key(gp_amp, lengths, coeffm):
+    return (float(gp_amp), tuple(float(v) for v in np.asarray(lengths).reshape(-1)), tuple(float(v) for v in np.asarray(coeffm).reshape(-1)))
 
 
 class Inversion:
@@ -128,6 +134,7 @@ class Inversion:
         and its exact gradient (PosteriorEngine.logl_grad)."""
         A_g, A_m = self._operators()
         lengths = create_cov_lengths(gp_length)  # in-place edit of the caller's array, like create_cov
+        self._step_params = None   # (set below once the step has returned: what the engine's factor was built from)
         ng, nm = self.gravfield.size, self.magfield.size
         args = (A_g, A_m, self._sel, self.Fs3[:ng], self.Fs3[ng:ng + nm], self.Fs3[ng + nm:], [float(v) for v in lengths],
                 self.coeffm if coeffm is None else coeffm, self.settings.kernelfunc, self.gp_sigma)
@@ -137,7 +144,9 @@ class Inversion:
         else:
             step = lambda: self.engine.logl_grad(*args, gp_amp, directions)
         try:
-            return step()
+            r = step()
+            self._step_params = _hyper_key(gp_amp, lengths, self.coeffm if coeffm is None else coeffm)
+            return r
         except FactorisationTimeout:
             # (round-5 advisory) the tile DAG's bounded spins can trip on a device shared with other processes: once more, on the
             # stream schedule of rounds 2-4 (no inter-workgroup hand-offs), instead of returning an undefined factor
@@ -147,7 +156,9 @@ class Inversion:
             before = os.environ.get("GEOBO_POTRF")
             os.environ["GEOBO_POTRF"] = "streams"
             try:
-                return step()
+                r = step()
+                self._step_params = _hyper_key(gp_amp, lengths, self.coeffm if coeffm is None else coeffm)
+                return r
             finally:
                 if before is None:
                     os.environ.pop("GEOBO_POTRF", None)
@@ -345,7 +356,87 @@ class Inversion:
         # deviations from the data means, back in data units (the means themselves are not restored, inversion.py:242-247)
         # (the std scalars keep the survey's dtype: a float32 survey squares its std in float32, as the reference does)
         scale = (grav_std, magn_std, drill_std)
+        self._cube_scale = scale
         with np.errstate(all="ignore"):
             rec = [mean_cubes[i] * scale[i] for i in range(3)]
             var = [var_cubes[i] * scale[i] ** 2 for i in range(3)]
         return rec[0], rec[1], rec[2], var[0], var[1], var[2]
+
+    # ---- posterior realisations ---------------------------------------------------------------------------
+    def _prior_sampler(self, approximate):
+        """PriorSampler of the current hyper-parameters (cached per grid, kernel, lengths, weights, amplitude)."""
+        s = self.settings
+        lengths = create_cov_lengths(np.array(self.gp_length, dtype=float))
+        args = ((s.yNcube, s.xNcube, s.zNcube), (s.xvoxsize, s.yvoxsize, s.zvoxsize), s.kernelfunc, [float(v) for v in lengths],
+                weight_matrix(self.coeffm), float(self.gp_amp))
+        key = (args[0], args[1], args[2], tuple(args[3]), tuple(map(tuple, args[4])), args[5], bool(approximate))
+        hit = getattr(self, "_sampler_cache", None)
+        if hit is None or hit[0] != key:
+            hit = self._sampler_cache = (key, PriorSampler(*args, device=self.engine.device, approximate=approximate))
+        return hit[1]
+
+    def _sample_cubes(self, f, scale=(1.0, 1.0, 1.0)):
+        s = self.settings
+        h = f.cpu().numpy().reshape(f.shape[0], 3, s.yNcube, s.xNcube, s.zNcube)
+        with np.errstate(all="ignore"):
+            return tuple(h[:, i] * scale[i] for i in range(3))
+
+    def sample_prior(self, n, seed=0, start=0, approximate=False):
+        """n realisations of the prior N(0, K) of create_cov (current gp_amp, gp_length, coeffm), drawn on the device by circulant
+        embedding: three arrays (n, yN, xN, zN) in the GP's normalised units.  Sample k (start <= k < start + n) depends only on (seed, k).
+        A prior whose cross-spectra are indefinite (possible with three distinct lengths and large weights) raises SamplingError;
+        approximate=True clips the negative eigenvalues of every frequency's 3 x 3 spectrum instead and returns the clipped fraction
+        (clipped trace / trace) as a fourth element."""
+        smp = self._prior_sampler(approximate)
+        out = self._sample_cubes(smp.sample(int(start), int(n), seed=int(seed)))
+        return out + (smp.clipped_fraction,) if approximate else out
+
+    def sample_posterior(self, n, seed=0, start=0, approximate=False, batch=None, prior=None, noise=None):
+        """n realisations of the joint posterior of the last cubing() survey, by Matheron's rule on the device:
+            f_post = f + K A3^T H^-1 (y - A3 f - eps),   f ~ N(0, K) (sample_prior),  eps ~ N(0, Sigma),  H = A3 K A3^T + Sigma,
+        which has exactly the posterior law N(mu, K - K A3^T H^-1 A3 K).  Returns three arrays (n, yN, xN, zN) in cubing()'s units (times
+        the data std of each block), so their mean tends to cubing()'s first three cubes.  Sample k depends only on (seed, k): start
+        addresses realisations, batch (default 64, at most 256) only bounds device memory.  The factor of the current hyper-parameters is reused, or
+        rebuilt (without the mean and variance) when the last step used others.
+        approximate=True (indefinite prior, see sample_prior): the clipped part E of the prior spectra leaves the samples' covariance off
+        by (I - G A3) E (I - G A3)^T, G = K A3^T H^-1; the clipped fraction is returned as a fourth element.
+        Tests: prior = (n, 3, N) array of f, noise = (n, M) array of eps (rows grav | magn | drill) replace the generators."""
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("sample_posterior() conditions on the survey of cubing(): call cubing() first")
+        s = self.settings
+        eng = self.engine
+        want = _hyper_key(self.gp_amp, create_cov_lengths(np.array(self.gp_length, dtype=float)), self.coeffm)
+        if getattr(self, "_step_params", None) != want or eng.last is None or tuple(eng.last["props"]) != (0, 1, 2):
+            self._run(self.gp_amp, self.gp_length, None, False, False)
+        # (with the caller's f only the exact spectra of K are used: an indefinite prior is no obstacle there)
+        smp = self._prior_sampler(approximate or prior is not None)
+        A_g, A_m = self._operators()
+        ng, nm = self.gravfield.size, self.magfield.size
+        y_g, y_m, y_d = self.Fs3[:ng], self.Fs3[ng:ng + nm], self.Fs3[ng + nm:]
+        M = ng + nm + y_d.size
+        sig = np.concatenate([np.full(ng, float(self.gp_sigma[0])), np.full(nm, float(self.gp_sigma[1])), np.full(y_d.size, float(self.gp_sigma[2]))])
+        sig_t = torch.as_tensor(sig, dtype=torch.float64, device=eng.device)
+        n, start = int(n), int(start)
+        # conditioning transforms two samples per complex line: sample k always shares it with sample k ^ 1 (batches start at even
+        # absolute indices and hold an even count, at most 256 -- one GEMM tile of rows), so its bits do not depend on the batching
+        batch = max(2, min(256, int(batch or 64)) // 2 * 2)
+        lo, hi = start - start % 2, start + n + (start + n) % 2
+
+        def given(a, b0, nb, shape):
+            out = np.zeros((nb,) + shape)
+            i0, i1 = max(b0, start), min(b0 + nb, start + n)
+            out[i0 - b0:i1 - b0] = np.asarray(a, dtype=np.float64)[i0 - start:i1 - start].reshape((i1 - i0,) + shape)
+            return torch.as_tensor(out, device=eng.device)
+        parts, ws, es = [], [], []
+        for b0 in range(lo, hi, batch):
+            nb = min(batch, hi - b0)
+            f = given(prior, b0, nb, (3, eng.N)) if prior is not None else smp.sample(b0, nb, seed=int(seed))
+            e = given(noise, b0, nb, (M,)) if noise is not None else observation_noise(int(seed), b0, nb, M, device=eng.device) * sig_t
+            fp, w = eng.condition(f, e, A_g, A_m, y_g, y_m, y_d, smp)
+            i0, i1 = max(b0, start) - b0, min(b0 + nb, start + n) - b0
+            parts.append(self._sample_cubes(fp[i0:i1], self._cube_scale))
+            ws.append(w[i0:i1].cpu().numpy())
+            es.append(e[i0:i1].cpu().numpy())
+        self.sample_info = dict(noise=np.concatenate(es), w=np.concatenate(ws), clipped_fraction=smp.clipped_fraction)
+        out = tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+        return out + (smp.clipped_fraction,) if approximate else out

@@ -36,6 +36,14 @@ def run(settings, method="auto", bayesopt=True, write=True):
         for c, n in zip(cubes, names):
             dataio.create_vtkcube(c, origin, voxelsize, fname=os.path.join(s.outpath, n + ".vtk"))
     out = dict(zip(names, cubes), inversion=inv, drillcoord=drillcoord, inputs=(gravfield, magfield, drillfield, sensor_locations, drilldata0))
+    nsamp = int(getattr(s, "posterior_samples", 0) or 0)     # optional YAML keys posterior_samples (default 0) and sample_seed
+    if nsamp > 0:
+        samples = inv.sample_posterior(nsamp, seed=int(getattr(s, "sample_seed", 0) or 0))
+        out["posterior_samples"] = samples
+        if write:
+            for c, n in zip(samples, ("density", "magsus", "drill")):
+                for k in range(nsamp):
+                    dataio.create_vtkcube(c[k], origin, voxelsize, fname=os.path.join(s.outpath, "cube_%s_sample_%03d.vtk" % (n, k)))
     if bayesopt:
         acq = Acquisition(s, cubes[2], cubes[5])
         if getattr(s, "bayesopt_vertical", False):

@@ -38,7 +38,9 @@ extern "C" {
 
 /* Additive since 212, version unchanged: covariance ids 7-15 (partial derivatives in the lengths, accepted by geobo_k_block,
  * geobo_k_block_f32, geobo_k_eval, geobo_cov_table and geobo_ak_fused), geobo_kinv_dot and geobo_kinv_dot_ws_bytes.  No existing
- * entry point, id or layout changed. */
+ * entry point, id or layout changed.
+ * Also additive since 212, version unchanged: the prior sampler of sampling.hip (geobo_philox_fill, geobo_torus_table,
+ * geobo_fft_lines, geobo_fft_axis, geobo_sample_factor, geobo_sample_factor_ws_bytes, geobo_sample_zpass, geobo_spectral_mix). */
 
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
@@ -533,6 +535,60 @@ int geobo_mfma_f64_peak(int blocks, int iters, double* out, void* stream);
 /* co-issue probe: `nv` VALU ops (mode 1 fp64 fma, 2 fp32 fma, 3 int mad; 0 none) after every fp64 MFMA of the same
  * wave; used to decide what the generator stage may cost (DESIGN.md section 4 "what shares the fp64 pipe"). */
 int geobo_mfma_mix(int mode, int nv, int blocks, int iters, double* out, void* stream);
+
+/* ---- prior sampler by circulant embedding (sampling.hip) ---------------------------------------------------
+ * Torus (my, mx, mz): powers of two, each >= 2n of its grid axis.  Complex arrays are interleaved fp64 (re, im).  Frequency index
+ * w = (wy mx + wx) mz + wz; octant index (fy (mx/2+1) + fx)(mz/2+1) + fz with f = min(w, m - w) per axis (the tables are even in
+ * every axis).  Block pairs i <= j of P <= 3 properties are numbered in row order of the upper triangle. */
+enum { GEOBO_RNG_PRIOR = 0, GEOBO_RNG_OBS = 1 };   /* purpose word of the Philox counter */
+#define GEOBO_FFT_INVERSE 1   /* exp(+2 pi i jk/m) instead of exp(-2 pi i jk/m); no scaling either way                       */
+#define GEOBO_FFT_IN_PAIRS 2  /* input: reals of an (S, P, Q) array, sample 2k = real part, 2k+1 = imaginary part of pair k      */
+#define GEOBO_FFT_OUT_PAIRS 4 /* output: the same packing, written as reals (samples >= S are not written)                      */
+#define GEOBO_FFT_MAX 512
+
+/* Counter-based Philox4x64-10, key (seed, 0), counter (elem0 + e, sample0 + s, purpose, sub) for s < nsamples, e < nelem:
+ * out[(s nelem + e) 4 + t], t < 4.  mode 1: the four raw 64-bit words (out read as uint64); mode 0: four fp64 normals, Box-Muller
+ * of words (0, 1) and (2, 3) with uniforms ((x >> 11) + 0.5) 2^-53: r cos(2 pi u1), r sin(2 pi u1), r = sqrt(-2 log u0).
+ * Every value depends on (seed, purpose, sample, element, sub) only.  Observation noise of sample s, element e is normal e % 4 of
+ * block (e / 4, s, GEOBO_RNG_OBS, 0). */
+int geobo_philox_fill(int mode, uint64_t seed, uint64_t purpose, int64_t sample0, int64_t nsamples, int64_t elem0, int64_t nelem,
+                      uint64_t sub, double* out, void* stream);
+
+/* out[w] = (w amp k(d2), 0), d2 the squared distance of the wrapped lag (min(d, m - d) per axis) with the operation order of
+ * geobo_cov_table: its crop to lags < n equals the blocks of geobo_k_block bit for bit.  kernel_id: families 1-6. */
+int geobo_torus_table(int kernel_id, int my, int mx, int mz, double sx, double sy, double sz, double l1, double l2, double w, double amp,
+                      double* out, void* stream);
+
+/* Lines per workgroup of geobo_fft_axis for an axis of length m over b1 inner columns (0: unsupported m). */
+int geobo_fft_lines(int m, int64_t b1);
+
+/* Batched complex fp64 Stockham FFT (radix 4, one radix-2 stage for odd log2 m) along the middle axis of a [b0][len][b1] array,
+ * whole lines in LDS: out[b0][k][b1] = sum_{j < n_in} in[b0][j][b1] exp(-+2 pi i jk/m) for k < n_out; in has n_in entries along the
+ * axis (the rest of the line is zero), out n_out (crop as you go).  m: power of two in 2 .. GEOBO_FFT_MAX.  b1 == 1: several whole
+ * contiguous lines per workgroup; b1 > 1: a tile of up to 4096/m adjacent columns.  flags: GEOBO_FFT_*; with the pair flags the
+ * packed side is an (S, P, Q) real array, Q = the elements of one (pair, property) slice.  in != out. */
+int geobo_fft_axis(int flags, int64_t b0, int m, int64_t b1, int n_in, int n_out, const double* in, double* out, int P, int64_t Q,
+                   int64_t S, void* stream);
+
+/* Per octant frequency: S(w) = [Re spectra[pair(i, j)][w]] (spectra: P(P+1)/2 complex torus arrays), eigen-decomposition by cyclic
+ * Jacobi in registers, F(w) = V diag(sqrt(max(e, 0))) (F F^T = S clipped to PSD): F[o][i][k], lam[o][pair] = the unclipped S.
+ * status (4 doubles): min eigenvalue, max eigenvalue, clipped trace, trace (over the whole torus: octant points weighted by the
+ * number of frequencies they stand for).  ws: geobo_sample_factor_ws_bytes() bytes; fixed-order reduction, no atomics. */
+size_t geobo_sample_factor_ws_bytes(void);
+int geobo_sample_factor(int P, int my, int mx, int mz, const double* spectra, double* F, double* lam, void* ws, size_t ws_bytes,
+                        double* status, void* stream);
+
+/* Fused first stage of the sampler for sample pairs pair0 .. pair0 + npairs: complex noise xi_q(w) (noise == NULL: Philox normals
+ * 2q, 2q + 1 of blocks (w, pair, GEOBO_RNG_PRIOR, 0 / 1); else noise[((k M + w) P + q)] complex, k relative to pair0), times
+ * F(w) / sqrt(my mx mz), inverse FFT along z, the first nz outputs: out[(k P + i)][wy][wx][iz] complex.  The x and y passes follow
+ * with geobo_fft_axis (the y pass with GEOBO_FFT_OUT_PAIRS writes samples 2k, 2k + 1 into (S, P, N)). */
+int geobo_sample_zpass(int P, int64_t pair0, int64_t npairs, int my, int mx, int mz, int nz, const double* F, const double* noise,
+                       uint64_t seed, double* out, void* stream);
+
+/* out[(k P + i) M + w] = scale sum_j lam[o(w)][pair(i, j)] in[(k P + j) M + w] for k < npairs: the covariance product on the torus
+ * (K v = crop(IFFT(lambda FFT(pad v))) / M).  in != out. */
+int geobo_spectral_mix(int P, int64_t npairs, int my, int mx, int mz, const double* lam, double scale, const double* in, double* out,
+                       void* stream);
 
 #ifdef __cplusplus
 }
