@@ -90,6 +90,8 @@ SIGNATURES = {
     "geobo_sample_factor": (_int, [_int, _int, _int, _int, _dp, _dp, _dp, _dp, _sz, _dp, _dp]),
     "geobo_sample_zpass": (_int, [_int, _i64, _i64, _int, _int, _int, _int, _dp, _dp, C.c_uint64, _dp, _dp]),
     "geobo_spectral_mix": (_int, [_int, _i64, _int, _int, _int, _dp, _f64, _dp, _dp, _dp]),
+    "geobo_set_gram": (_int, [_i64, _int, _dp, _i64, _dp, _i64, _i64, _int, _dp, _dp]),
+    "geobo_set_logdet": (_int, [_i64, _int, _dp, _dp, _i64, _f64, _dp, _dp, _i64, _dp, _dp, _dp]),
     "geobo_trmv_stats": (_int, [_i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _dp]),
     "geobo_mfma_f64_peak": (_int, [_int, _int, _dp, _dp]),
     "geobo_mfma_mix": (_int, [_int, _int, _int, _int, _dp, _dp]),

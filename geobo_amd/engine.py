@@ -43,6 +43,7 @@ from .columnform import ColumnExchangeMixin
 from .rowform import RowFormMixin
 from .operators import StreamedOperator
 from .transposed import TransposedPosteriorMixin
+from .information import SetStatisticsMixin
 from .sharding import (EmulatedGroup, allreduce_sum_, assemble_columns, backend_of, exchange_blocks, exchange_blocks_finish,
                        exchange_blocks_start, gather_rows, gather_slices, shard_columns)
 
@@ -165,7 +166,7 @@ def _on_device(fn):
     return wrapper
 
 
-class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixin):
+class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixin, SetStatisticsMixin):
     def __init__(self, settings, device=None, rank=0, world=1, group=None, profile=False, method="auto", assembly="f64",
                  operators="resident"):
         """assembly "f32": covariance tables rounded through fp32 and A K kept in fp32 in HBM (BASELINE config 5, "fp32 kernel
@@ -1044,7 +1045,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         # A K is published only when it is whole; the symmetric plan leaves the blocks (magn rows, block 0) and (sensor rows, block 2)
         # unwritten: that buffer goes under AK_partial (the tests' oracle contacts read its assembled blocks); the row form has none
         whole = AK is not None and not self._ak_sym
-        self.last = dict(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props, sel=sel)
+        self.last = dict(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props, sel=sel,
+                         ops=(A_g, A_m))
         return out
 
     def _derivative_gram(self, A_g, A_m, sel_t, lengths, W, name, amp, props, provider, slot):

@@ -793,6 +793,56 @@ def kinv_dot(Linv, alpha, Gs, segs, ws=None, out=None):
     return out
 
 
+def set_gram(idx, V, R, G, accumulate=False, ncols=None):
+    """G[c] = (accumulate ? G[c] : 0) + V[:R, idx[c]]^T V[:R, idx[c]] for the C sets of idx ((C, k) int32, k <= 128; entries outside
+    [0, ncols) are padding).  V: 2-D fp64 rows of V_d (columns in voxel order); G: (C, k, k) fp64, written in full (fp64 MFMA)."""
+    lib = require_gpu()
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.is_contiguous()):
+        raise TypeError("idx must be a contiguous (C, k) CUDA int32 tensor")
+    C_, k = idx.shape
+    ldv = _rowmajor(V, "V")
+    R = int(R)
+    assert 0 <= R <= V.shape[0]
+    ncols = V.shape[1] if ncols is None else int(ncols)
+    assert ncols <= V.shape[1]
+    _chk(G, "G")
+    assert G.is_contiguous() and tuple(G.shape) == (C_, k, k)
+    _lib.check(lib.geobo_set_gram(C_, k, _p(idx), R, _p(V), ldv, ncols, 1 if accumulate else 0, _p(G), _stream()), "geobo_set_gram")
+    return G
+
+
+def set_logdet(G, Kpp, sigma2, idx, n_obs, observed=None, out=None, status=None):
+    """Per set c: D = Kpp_c - G[c], S = D / sigma2 + I (entries that are padding or `observed` become unit rows / columns), Cholesky:
+    out (3, C) = [1/2 log det S, 1^T D 1, trace D] over the entries kept, status (C,) int32 = 0 or 1 + failing pivot (NaN outputs).
+    Kpp: (k, k) shared by every set or (C, k, k) one per set; observed: (n_obs,) uint8 CUDA tensor or None."""
+    lib = require_gpu()
+    C_, k = idx.shape
+    _chk(G, "G")
+    _chk(Kpp, "Kpp")
+    if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
+        raise TypeError("idx must be a contiguous (C, k) CUDA int32 tensor")
+    assert G.is_contiguous() and tuple(G.shape) == (C_, k, k) and Kpp.is_contiguous()
+    if tuple(Kpp.shape) == (k, k):
+        stride = 0
+    elif tuple(Kpp.shape) == (C_, k, k):
+        stride = k * k
+    else:
+        raise ValueError("Kpp must be (k, k) or (C, k, k)")
+    obs = None
+    if observed is not None:
+        if not (isinstance(observed, torch.Tensor) and observed.is_cuda and observed.dtype == torch.uint8 and observed.is_contiguous()
+                and observed.numel() >= int(n_obs)):
+            raise TypeError("observed must be a contiguous CUDA uint8 tensor of n_obs entries")
+        obs = _p(observed)
+    if out is None:
+        out = torch.empty((3, C_), dtype=F64, device=G.device)
+    if status is None:
+        status = torch.empty(C_, dtype=torch.int32, device=G.device)
+    _lib.check(lib.geobo_set_logdet(C_, k, _p(G), _p(Kpp), stride, float(sigma2), _p(idx), obs, int(n_obs), _p(_chk(out, "out")),
+                                    _p(status), _stream()), "geobo_set_logdet")
+    return out, status
+
+
 def mfma_f64_peak(blocks=1024, iters=20000):
     """Time the v_mfma_f64_16x16x4_f64 issue rate; returns TFLOP/s (4 waves/WG x 16 MFMA x 2048 flop per iter)."""
     lib = require_gpu()

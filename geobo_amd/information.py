@@ -1,0 +1,190 @@
+"""Per-set blocks of the drill-property posterior covariance: mixin of engine.PosteriorEngine.
+
+For a voxel set P (a drill hole) the posterior covariance of the drill property is
+
+    Sigma_PP = K_dd(P, P) - G_P,   G_P = V_d(:, P)^T V_d(:, P),   V_d = (L^-1 A3 K)[:, drill block]
+
+from the factor of the last posterior() step.  V_d (M x N) is never stored: it is produced tile by tile of rows, and every tile goes
+through geobo_set_gram, which adds V_tile(:, P_c)^T V_tile(:, P_c) to G[c] for every set c at once.  geobo_set_logdet then forms
+S_c = Sigma_PP / sigma_d^2 + I and returns 1/2 log det S_c (the information gain of a drill log along P, nats), 1^T Sigma_PP 1 and
+trace Sigma_PP.
+
+Two sources of V_d tiles, by the route the step took:
+  spectral  the transposed route (plan.Route.single): rows of Z = L^-1 A3 as the step makes them (lattice convolutions or MFMA GEMMs
+            against the operators), times K through SpectralProduct.product with the generators of blocks (0, 2), (1, 2), (2, 2);
+            the drill term only in the rows behind the sensor rows (L^-1 is lower triangular), as in _drill_rows_ss.
+  generic   every other one-rank fp64 step: L^-1 (A K)[:, drill block] by MFMA GEMMs when A K is whole, otherwise rows of Z by
+            GEMMs against the operator rows (as condition() forms A3^T W) and K through the prior sampler's exact circulant product.
+"""
+import numpy as np
+import torch
+
+from . import hip
+
+F64 = hip.F64
+SET_K_MAX = 128
+
+
+def _vertical_bases(idx, nz):
+    """Column bases when every set is one whole z-column (nz contiguous flat indices from a multiple of nz), else None."""
+    idx = np.asarray(idx)
+    if idx.shape[1] != nz:
+        return None
+    base = idx[:, 0]
+    if np.any(base < 0) or np.any(base % nz) or not np.array_equal(idx, base[:, None] + np.arange(nz)[None, :]):
+        return None
+    return base
+
+
+class SetStatisticsMixin:
+    def _set_sampler(self, name, lengths, W, amp):
+        """PriorSampler whose exact circulant product applies K (generic source), cached per hyper-parameters."""
+        from .sampling import PriorSampler
+        s = self.s
+        key = (name, tuple(float(v) for v in lengths), tuple(map(tuple, W)), float(amp))
+        hit = getattr(self, "_set_smp", None)
+        if hit is None or hit[0] != key:
+            smp = PriorSampler((self.ny, self.nx, self.nz), (s.xvoxsize, s.yvoxsize, s.zvoxsize), name, [float(v) for v in lengths], W,
+                               float(amp), device=self.device, approximate=True)
+            hit = self._set_smp = (key, smp)
+        return hit[1]
+
+    def _vd_spectral(self, Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m):
+        """Tiles (V, n) of 128 rows of V_d on the transposed route, voxel order (iy, ix, iz)."""
+        sp, N, Msp, T = self._spectral, self.N, self.Ms_pad, 128
+        lat = (self._gram is not None and self._gram.edge_supported() and Msp == self.nx * self.ny and self.route.opt("z_lattice")
+               and all(self._lam.get(f) is not None and self._lam[f][0] is A for f, A in (("grav", A_g), ("magn", A_m))))
+        if not lat:
+            Ag = self._resident_operator(A_g, "grav")
+            Am = self._resident_operator(A_m, "magn")
+        gens = [self._gens[(0, 2)], self._gens[(1, 2)],
+                sp.eigenvalues(self._cov_table(hip.kernel_id(name, False), lengths[2], lengths[2], W[2][2], amp))]
+        Zg, Zm, Zd, V, tmp = (self._workspace2d(nm, T, N) for nm in ("set_Zg", "set_Zm", "set_Zd", "set_V", "set_Vt"))
+        Mv = 2 * Msp + Md
+        for b0 in range(0, Mv, T):
+            n = min(T, Mv - b0)
+            terms = []
+            for func, A, Ar, c0, Z, g in (("grav", A_g, None if lat else Ag, 0, Zg, gens[0]), ("magn", A_m, None if lat else Am, Msp, Zm, gens[1])):
+                if b0 + n <= c0:
+                    continue                                # L^-1 is lower triangular: these rows do not see this operator
+                if lat:
+                    self._lattice_Z(Linv[b0:b0 + n, c0:c0 + Msp], n, func, A, Z)
+                else:
+                    hip.gemm_nn(Linv[b0:b0 + T, c0:c0 + Msp], Ar[:Msp, :N], Z)
+                terms.append((Z, g))
+            if Md and b0 + n > 2 * Msp:
+                Zd[:n].zero_()
+                Zd[:n, sel_t] = Linv[b0:b0 + n, 2 * Msp:2 * Msp + Md]
+                terms.append((Zd, gens[2]))
+            sp.product(terms[0][0], n, [terms[0][1]], [V])
+            for Z, g in terms[1:]:
+                sp.product(Z, n, [g], [tmp])
+                V[:n].add_(tmp[:n])
+            yield V, n
+
+    def _vd_generic(self, Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m, AK):
+        """Tiles (V, n) of 256 rows of V_d on any one-rank fp64 step, voxel order (iy, ix, iz)."""
+        N, Np, Msp, T = self.N, self.N_pad, self.Ms_pad, 256
+        Mv = 2 * Msp + Md
+        if AK is not None:
+            d0 = 2 * self.nc
+            AKd = AK[:, d0:d0 + Np]
+            V = self._workspace2d("set_V", T, Np)
+            for b0 in range(0, Mv, T):
+                e = b0 + T                                  # (M_pad is a multiple of 256: whole tiles; columns >= e of L^-1 are zero)
+                hip.gemm_nn(Linv[b0:e, :e], AKd[:e], V)
+                yield V, min(T, Mv - b0)
+            return
+        smp = self._set_sampler(name, lengths, W, amp)
+        Zt = torch.empty((T, 3, N), dtype=F64, device=self.device)
+        Zp = self._workspace2d("set_Zp", T, Np)
+        for b0 in range(0, Mv, T):
+            n = min(T, Mv - b0)
+            for j, A, r0 in ((0, A_g, 0), (1, A_m, Msp)):
+                if b0 + n <= r0:
+                    Zt[:, j, :].zero_()
+                    continue
+                for c0, rows in self._operator_rows(A):
+                    hip.gemm_nn(Linv[b0:b0 + T, r0 + c0:r0 + c0 + rows.shape[0]], rows, Zp, beta=1.0 if c0 else 0.0)
+                Zt[:, j, :] = Zp[:, :N]
+            Zt[:, 2, :].zero_()
+            if Md and b0 + n > 2 * Msp:
+                Zt[:, 2, :][:, sel_t] = Linv[b0:b0 + T, 2 * Msp:2 * Msp + Md]
+            KZ = smp.apply_K(Zt[:n])
+            yield KZ[:, 2, :], n
+
+    def set_statistics(self, sets, kernelfunc, lengths, crossweights, gp_amp, gp_sigma, observed=None, source="auto"):
+        """Posterior statistics of the drill property over C voxel sets, from the factor of the last posterior() step:
+            info_gain[c] = 1/2 log det(I + Sigma_PP / sigma_d^2)  (nats),  path_var[c] = 1^T Sigma_PP 1,  sum_var[c] = trace Sigma_PP,
+        P = sets[c] (flat voxel indices in (iy, ix, iz) order; entries < 0 are padding), sigma_d = gp_sigma[2], all in the GP's
+        normalised units.  observed: optional (N,) bool mask of voxels that already carry a drill row: they are left out (unit rows of
+        S, not in the sums).  `lengths` carry the create_cov mutation.  source: "auto" (by the step's route), "spectral" or "generic".
+        Returns device tensors (info_gain, path_var, sum_var, status), C each; status 1 + pivot marks a set whose S did not factorise
+        (NaN outputs).  One rank, fp64 assembly, a step over property blocks (0, 1, 2)."""
+        from .engine import weight_matrix
+        if self.world > 1:
+            raise NotImplementedError("set statistics run on one rank (world = %d)" % self.world)
+        last = self.last
+        if last is None or tuple(last["props"]) != (0, 1, 2):
+            raise RuntimeError("set_statistics() needs the factor of a posterior() step over all three property blocks")
+        AK = last["AK"] if last["AK_complete"] else last["AK_partial"]
+        if self.f32 or (AK is not None and AK.dtype != F64):
+            raise NotImplementedError("set statistics need the fp64 assembly")
+        sets = np.asarray(sets)
+        if sets.ndim != 2 or not 1 <= sets.shape[1] <= SET_K_MAX:
+            raise ValueError("sets must be a (C, k) index table with 1 <= k <= %d" % SET_K_MAX)
+        if np.any(sets >= self.N):
+            raise ValueError("set entries must be flat voxel indices below N = %d (negative: padding)" % self.N)
+        with torch.cuda.device(self.device):
+            return self._set_statistics(sets.astype(np.int64), kernelfunc, lengths, weight_matrix(crossweights), float(gp_amp),
+                                        float(gp_sigma[2]) ** 2, observed, source, AK)
+
+    def _set_statistics(self, sets, name, lengths, W, amp, sigma2, observed, source, AK):
+        last = self.last
+        Linv = last["Linv"]
+        A_g, A_m = last["ops"]
+        sel = np.asarray(last["sel"], dtype=np.int64)
+        Md = len(sel)
+        sel_t = torch.as_tensor(sel, device=self.device) if Md else None
+        C_, k = sets.shape
+        dev = self.device
+        idx = torch.as_tensor(sets.astype(np.int32), device=dev)
+        G = torch.zeros((C_, k, k), dtype=F64, device=dev)
+        spectral_ok = self._zpath_ok(AK, (0, 1, 2), A_g, A_m)
+        if source == "auto":
+            source = "spectral" if spectral_ok else "generic"
+        if source == "spectral" and not spectral_ok:
+            raise RuntimeError("the spectral source needs a step on the transposed route")
+        if source not in ("spectral", "generic"):
+            raise ValueError("source must be 'auto', 'spectral' or 'generic'")
+        self.set_source = source
+        if source == "spectral":
+            tiles = self._vd_spectral(Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m)
+        else:
+            tiles = self._vd_generic(Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m, AK if last["AK_complete"] else None)
+
+        def sweep():
+            first = True
+            for V, n in tiles:
+                hip.set_gram(idx, V, n, G, accumulate=not first, ncols=self.N)
+                first = False
+        self._timed("set_sweep", 0.0, sweep)
+        # prior block K_dd(P, P): one block for whole z-columns (the prior is stationary), else one per set
+        xyz = self.grid_points()
+        kid = hip.kernel_id(name, False)
+        base = _vertical_bases(sets, self.nz)
+        if base is not None:
+            col = torch.as_tensor(np.arange(k) + int(base[0]) if C_ else np.arange(k), device=dev)
+            Kpp = torch.empty((k, k), dtype=F64, device=dev)
+            hip.k_block(kid, tuple(c[col] for c in xyz), tuple(c[col] for c in xyz), lengths[2], lengths[2], W[2][2], amp, Kpp)
+        else:
+            Kpp = torch.empty((C_, k, k), dtype=F64, device=dev)
+            pts = torch.as_tensor(np.maximum(sets, 0), device=dev)
+            for c in range(C_):
+                p = tuple(x[pts[c]] for x in xyz)
+                hip.k_block(kid, p, p, lengths[2], lengths[2], W[2][2], amp, Kpp[c])
+        obs = None
+        if observed is not None:
+            obs = torch.as_tensor(np.asarray(observed, dtype=bool).reshape(-1)[:self.N].astype(np.uint8), device=dev)
+        out, status = self._timed("set_logdet", 0.0, lambda: hip.set_logdet(G, Kpp, sigma2, idx, self.N, observed=obs))
+        return out[0], out[1], out[2], status

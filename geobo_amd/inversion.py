@@ -440,3 +440,125 @@ class Inversion:
         self.sample_info = dict(noise=np.concatenate(es), w=np.concatenate(ws), clipped_fraction=smp.clipped_fraction)
         out = tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
         return out + (smp.clipped_fraction,) if approximate else out
+
+    # ---- drill-hole information gain and greedy campaigns ------------------------------------------------
+    def _cubing_done(self, what):
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("%s scores holes against the posterior of cubing(): call cubing() first" % what)
+
+    def _set_stats(self, sets, observed=None):
+        """Engine set statistics of the current factor (normalised units), as host arrays."""
+        lengths = create_cov_lengths(np.array(self.gp_length, dtype=float))
+        r = self.engine.set_statistics(sets, self.settings.kernelfunc, [float(v) for v in lengths], self.coeffm, self.gp_amp, self.gp_sigma,
+                                       observed=observed)
+        return tuple(t.cpu().numpy() for t in r)
+
+    def _ensure_factor(self):
+        eng = self.engine
+        want = _hyper_key(self.gp_amp, create_cov_lengths(np.array(self.gp_length, dtype=float)), self.coeffm)
+        if getattr(self, "_step_params", None) != want or eng.last is None or tuple(eng.last["props"]) != (0, 1, 2):
+            self._run(self.gp_amp, self.gp_length, None, False, False)
+
+    def hole_statistics(self, paths=None):
+        """Posterior statistics of the drill property along holes, after cubing():
+            info_gain = 1/2 log det(I + Sigma_PP / sigma_d^2)  (nats, scale-free),  path_std = sqrt(1^T Sigma_PP 1),  sum_var = trace Sigma_PP
+        (the last two in cubing()'s drill units).  paths=None: (yN, xN) tables of every vertical hole (NaN on the rim); else a list of
+        Acquisition.path_voxels triplets (dipping holes: the unique voxels of each path), one value per path (NaN for a path that
+        leaves the cube).  Returns dict(info_gain, path_std, sum_var, status)."""
+        from . import campaign
+        self._cubing_done("hole_statistics()")
+        s = self.settings
+        self._ensure_factor()
+        ds = float(self._cube_scale[2])
+        if paths is None:
+            sets, ij = campaign.vertical_sets(s.yNcube, s.xNcube, s.zNcube)
+            ig, pv, sv, st = self._set_stats(sets)
+            tab = lambda v: campaign.column_table(v, ij, s.yNcube, s.xNcube)
+            st_t = np.full((s.yNcube, s.xNcube), -1, dtype=np.int64)
+            st_t[ij[:, 0], ij[:, 1]] = st
+            return dict(info_gain=tab(ig), path_std=tab(np.sqrt(pv) * ds), sum_var=tab(sv * ds ** 2), status=st_t)
+        sets, valid = campaign.path_sets(paths, (s.yNcube, s.xNcube, s.zNcube))
+        out = dict(info_gain=np.full(len(valid), np.nan), path_std=np.full(len(valid), np.nan), sum_var=np.full(len(valid), np.nan),
+                   status=np.full(len(valid), -1, dtype=np.int64))
+        if valid.any():
+            ig, pv, sv, st = self._set_stats(sets[valid])
+            out["info_gain"][valid], out["path_std"][valid], out["sum_var"][valid], out["status"][valid] = ig, np.sqrt(pv) * ds, sv * ds ** 2, st
+        return out
+
+    def propose_drill_campaign(self, q, utility="information", costs=None, write=False):
+        """A greedy batch of q distinct vertical holes ("kriging believer"): pick the best inner hole by `utility` ("information",
+        "ucb", "ucb_path"; see geobo_amd.campaign), add its voxels that carry no drill row yet as drill rows whose values are the
+        posterior mean (which leaves the mean unchanged), refactor without the mean and variance, score again without the chosen holes.
+        The statistics leave out voxels that already carry a drill row (they would not be measured again); the mean and cost sums run
+        over the whole hole, as the reference's.  Returns a DataFrame (NORTHING, EASTING at voxel centres, RANK, UTILITY, INFO_GAIN,
+        PATH_STD) and sets `campaign_info` (chosen voxel sets, the three variance cubes after all q holes in cubing()'s units, and the
+        mean cubes of that step).  The Inversion is left as cubing() left it; the engine's factor is rebuilt from the real data."""
+        import os
+
+        import pandas as pd
+        from . import campaign
+        self._cubing_done("propose_drill_campaign()")
+        if utility not in campaign.UTILITIES:
+            raise ValueError("utility must be one of %s, got %r" % (campaign.UTILITIES, utility))
+        s = self.settings
+        ny, nx, nz = s.yNcube, s.xNcube, s.zNcube
+        N = nx * ny * nz
+        q = int(q)
+        if not 0 <= q <= (ny - 2) * (nx - 2):
+            raise ValueError("q must be between 0 and the %d inner vertical holes" % ((ny - 2) * (nx - 2)))
+        sets, ij = campaign.vertical_sets(ny, nx, nz)
+        ds = float(self._cube_scale[2])
+        scale = self._cube_scale
+        zsum = lambda a: np.ascontiguousarray(a).sum(axis=2)[ij[:, 0], ij[:, 1]]
+        drill_rec = self.mu_rec[2 * N:3 * N].reshape(ny, nx, nz) * scale[2]
+        cost = np.zeros((ny, nx, nz)) if costs is None else np.asarray(costs, dtype=float).reshape(ny, nx, nz)
+        mean_sum, cost_sum = zsum(drill_rec), zsum(cost)
+        mu_d = np.asarray(self.mu_rec[2 * N:3 * N], dtype=np.float64)          # normalised posterior mean of the drill block
+        ng, nm = self.gravfield.size, self.magfield.size
+        y_g, y_m = self.Fs3[:ng], self.Fs3[ng:ng + nm]
+        values = np.zeros(N)
+        values[self._sel] = self.Fs3[ng + nm:]
+        sel = np.asarray(self._sel, dtype=np.int64).copy()
+        lengths = [float(v) for v in create_cov_lengths(np.array(self.gp_length, dtype=float))]
+        eng = self.engine
+        A_g, A_m = self._operators()
+
+        def step(sel, want_mean_var):
+            return eng.posterior(A_g, A_m, sel, y_g, y_m, values[sel], lengths, self.coeffm, s.kernelfunc, self.gp_sigma, gp_amp=self.gp_amp,
+                                 props=(0, 1, 2), calclogl=False, want_mean_var=want_mean_var)
+        picks, rows = [], []
+        try:
+            self._step_params = None            # from here on the factor holds fantasised rows
+            for rank in range(q):
+                step(sel, False)
+                observed = np.zeros(N, dtype=bool)
+                observed[sel] = True
+                ig, pv, sv, st = (t.cpu().numpy() for t in eng.set_statistics(sets, s.kernelfunc, lengths, self.coeffm, self.gp_amp,
+                                                                                 self.gp_sigma, observed=observed))
+                u = campaign.utility(utility, mean_sum, cost_sum, s.kappa, s.beta, info_gain=ig, path_var=pv * ds ** 2, sum_var=sv * ds ** 2)
+                u = np.where(np.isfinite(u), u, -np.inf)
+                u[picks] = -np.inf
+                c = int(np.argmax(u))
+                if not np.isfinite(u[c]):
+                    raise RuntimeError("no hole left to score (statistics status %s)" % np.unique(st))
+                picks.append(c)
+                rows.append((ij[c, 0], ij[c, 1], rank + 1, float(u[c]), float(ig[c]), float(np.sqrt(pv[c])) * ds))
+                new = sets[c][~observed[sets[c]]]
+                values[new] = mu_d[new]
+                sel = np.union1d(sel, new)
+            r = step(sel, True)
+            shape = (3, ny, nx, nz)
+            with np.errstate(all="ignore"):
+                var = [r["var"].reshape(shape)[i] * scale[i] ** 2 for i in range(3)]
+                mean = [r["mu"].reshape(shape)[i] * scale[i] for i in range(3)]
+            self.campaign_info = dict(sets=[sets[c].copy() for c in picks], holes=ij[picks].copy(), selection=sel.copy(), var=var, mean=mean,
+                                      utility=utility)
+        finally:
+            # the engine's factor back to the real survey (sample_posterior must never condition on fantasised rows)
+            self._run(self.gp_amp, self.gp_length, None, False, False)
+        table = pd.DataFrame(rows, columns=["I0", "I1", "RANK", "UTILITY", "INFO_GAIN", "PATH_STD"])
+        table.insert(0, "NORTHING", table.pop("I0") * s.yvoxsize + s.ymin + 0.5 * s.yvoxsize)
+        table.insert(1, "EASTING", table.pop("I1") * s.xvoxsize + s.xmin + 0.5 * s.xvoxsize)
+        if write:
+            table.to_csv(os.path.join(s.outpath, "newdrill_campaign_vertical.csv"), index=False)
+        return table

@@ -44,6 +44,9 @@ def run(settings, method="auto", bayesopt=True, write=True):
             for c, n in zip(samples, ("density", "magsus", "drill")):
                 for k in range(nsamp):
                     dataio.create_vtkcube(c[k], origin, voxelsize, fname=os.path.join(s.outpath, "cube_%s_sample_%03d.vtk" % (n, k)))
+    ncamp = int(getattr(s, "drill_campaign", 0) or 0)      # optional YAML keys drill_campaign (q, default 0) and campaign_utility
+    if ncamp > 0:
+        out["drill_campaign"] = inv.propose_drill_campaign(ncamp, utility=getattr(s, "campaign_utility", None) or "information", write=write)
     if bayesopt:
         acq = Acquisition(s, cubes[2], cubes[5])
         if getattr(s, "bayesopt_vertical", False):

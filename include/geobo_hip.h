@@ -40,7 +40,9 @@ extern "C" {
  * geobo_k_block_f32, geobo_k_eval, geobo_cov_table and geobo_ak_fused), geobo_kinv_dot and geobo_kinv_dot_ws_bytes.  No existing
  * entry point, id or layout changed.
  * Also additive since 212, version unchanged: the prior sampler of sampling.hip (geobo_philox_fill, geobo_torus_table,
- * geobo_fft_lines, geobo_fft_axis, geobo_sample_factor, geobo_sample_factor_ws_bytes, geobo_sample_zpass, geobo_spectral_mix). */
+ * geobo_fft_lines, geobo_fft_axis, geobo_sample_factor, geobo_sample_factor_ws_bytes, geobo_sample_zpass, geobo_spectral_mix).
+ * Also additive since 212, version unchanged: the per-set posterior statistics of information.hip (geobo_set_gram,
+ * geobo_set_logdet). */
 
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
@@ -589,6 +591,25 @@ int geobo_sample_zpass(int P, int64_t pair0, int64_t npairs, int my, int mx, int
  * (K v = crop(IFFT(lambda FFT(pad v))) / M).  in != out. */
 int geobo_spectral_mix(int P, int64_t npairs, int my, int mx, int mz, const double* lam, double scale, const double* in, double* out,
                        void* stream);
+
+/* ---- per-set posterior statistics (information.hip) -------------------------------------------------------
+ * G[c] = (accumulate ? G[c] : 0) + sum_{r < R} V[r, idx[c a]] V[r, idx[c b]]  (a, b < k), for C sets of k <= 128 entries.
+ * idx: int32, C x k row-major; an entry outside [0, ncols) is padding (reads nothing).  V: R x ldv fp64 row-major (ldv >= ncols).
+ * G: C x k x k fp64, written in full (lower 16 x 16 tiles computed, mirrored).  fp64 MFMA, one workgroup per set, no atomics: tiles
+ * of the same rows split at multiples of 4 rows give the same bits.  Checks before any device access: NULL pointers, C < 0, k < 1,
+ * k > 128, R < 0, ldv < ncols (GEOBO_E_ARG).  C == 0 is a no-op. */
+int geobo_set_gram(int64_t C, int k, const int32_t* idx, int64_t R, const double* V, int64_t ldv, int64_t ncols, int accumulate,
+                   double* G, void* stream);
+
+/* Per set c: D = Kpp_c - G[c] (Kpp_c = Kpp + c kpp_stride, k x k row-major; kpp_stride 0: one block shared by every set) and
+ * S = D / sigma2 + I, where entry a is dropped (unit row and column of S, left out of both sums) when idx[c a] is outside
+ * [0, n_obs) or observed[idx[c a]] != 0 (observed: n_obs bytes, may be NULL).  Cholesky of S in LDS:
+ *   out[c] = 1/2 log det S,  out[C + c] = sum_ab D_ab,  out[2C + c] = sum_a D_aa  (over the entries kept),
+ *   status[c] = 0, or 1 + the first non-positive pivot, with NaN in the three outputs of that set (the other sets are unaffected).
+ * Checks before any device access: NULL pointers (but observed), C < 0, k < 1, k > 128, n_obs < 0, 0 < kpp_stride < k k,
+ * sigma2 not positive (GEOBO_E_ARG). */
+int geobo_set_logdet(int64_t C, int k, const double* G, const double* Kpp, int64_t kpp_stride, double sigma2, const int32_t* idx,
+                     const uint8_t* observed, int64_t n_obs, double* out, int* status, void* stream);
 
 #ifdef __cplusplus
 }
