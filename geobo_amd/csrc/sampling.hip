@@ -207,7 +207,12 @@ __device__ void jacobi_eig(double a[3][3], double v[3][3]) {
     if (!(off > 1e-34 * tot)) break;
     for (int p = 0; p < P - 1; ++p)
       for (int q = p + 1; q < P; ++q) {
-        if (a[p][q] == 0.0) continue;
+        // an off-diagonal below the rounding of its two diagonal entries is zero: rotating on it (repeated eigenvalues: a large
+        // angle set by noise) never converges and every such rotation costs V an eps of orthogonality
+        if (fabs(a[p][q]) <= 0x1p-54 * (fabs(a[p][p]) + fabs(a[q][q]))) {
+          a[p][q] = a[q][p] = 0.0;
+          continue;
+        }
         const double tau = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
         const double t = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
         const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
@@ -219,6 +224,7 @@ __device__ void jacobi_eig(double a[3][3], double v[3][3]) {
           const double apk = a[p][k], aqk = a[q][k];
           a[p][k] = c * apk - s * aqk; a[q][k] = s * apk + c * aqk;
         }
+        a[p][q] = a[q][p] = 0.0;   // what the rotation was chosen for
         for (int k = 0; k < P; ++k) {
           const double vkp = v[k][p], vkq = v[k][q];
           v[k][p] = c * vkp - s * vkq; v[k][q] = s * vkp + c * vkq;
