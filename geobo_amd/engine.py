@@ -44,6 +44,7 @@ from .rowform import RowFormMixin
 from .operators import StreamedOperator
 from .transposed import TransposedPosteriorMixin
 from .information import SetStatisticsMixin
+from .step import Prior, Step
 from .sharding import (EmulatedGroup, allreduce_sum_, assemble_columns, backend_of, exchange_blocks, exchange_blocks_finish,
                        exchange_blocks_start, gather_rows, gather_slices, shard_columns)
 
@@ -79,46 +80,6 @@ def weight_matrix(crossweights):
     """kernels.py:166-169,181 -- w1: 0<->2, w2: 1<->2, w3: 0<->1."""
     w1, w2, w3 = [float(v) for v in np.asarray(crossweights)]
     return [[1.0, w3, w1], [w3, 1.0, w2], [w1, w2, 1.0]]
-
-
-class DirectionalCov:
-    """Covariance provider of the derivative of K along a direction d in the three lengths (PosteriorEngine.logl_grad).
-    Block (row property i, column property j) of create_cov is w_ij k(l1 = l_j, l2 = l_i), so its directional derivative is
-    w_ij (d_j dk/dl1 + d_i dk/dl2); a self block has one length: w d_j dk/dl.  The blocks (i, j) and (j, i) stay transposes of each
-    other (k_ij(a, b) = k_ji(b, a)), so the derivative Gram is symmetric and runs through every route of the assembly unchanged."""
-
-    def __init__(self, d):
-        self.d = [float(v) for v in d]
-
-    def terms(self, name, i, j, W):
-        w = W[i][j]
-        if i == j:
-            return [(hip.kernel_id(name, False, 1), w * self.d[j])]
-        return [(hip.kernel_id(name, True, 1), w * self.d[j]), (hip.kernel_id(name, True, 2), w * self.d[i])]
-
-    def table(self, eng, name, i, j, lengths, W, amp):
-        tabs = [eng._cov_table(kid, lengths[j], lengths[i], w, amp) for kid, w in self.terms(name, i, j, W)]
-        for t in tabs[1:]:
-            tabs[0].add_(t)
-        return tabs[0]
-
-    def k_block(self, eng, name, i, j, rows, cols, lengths, W, amp, out):
-        terms = self.terms(name, i, j, W)
-        hip.k_block(terms[0][0], rows, cols, lengths[j], lengths[i], terms[0][1], amp, out)
-        for kid, w in terms[1:]:
-            tmp = eng._workspace2d("dcov_tmp", out.shape[0], out.shape[1])
-            hip.k_block(kid, rows, cols, lengths[j], lengths[i], w, amp, tmp)
-            out.add_(tmp)
-        return out
-
-    def ak_fused(self, eng, name, s_, j, A, xyz, nc, lengths, W, amp, out):
-        terms = self.terms(name, s_, j, W)
-        hip.ak_fused(terms[0][0], A, xyz, eng.c0, nc, lengths[j], lengths[s_], terms[0][1], amp, out)
-        for kid, w in terms[1:]:
-            tmp = eng._workspace2d("dak_tmp", out.shape[0], nc)
-            hip.ak_fused(kid, A, xyz, eng.c0, nc, lengths[j], lengths[s_], w, amp, tmp)
-            out[:, :nc].add_(tmp)
-        return out
 
 
 # weight -> the block pair it multiplies (weight_matrix): w1 on (0, 2), w2 on (1, 2), w3 on (0, 1)
@@ -224,7 +185,6 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self._lattice_plan = None
         self._gram, self._lam, self._edgeV = None, {}, {}
         self._lamW, self._edgeVt = {}, {}     # transposed lattice application: permuted eigen-data, boundary-slab spectra
-        self._gens = {}             # Toeplitz generators of the covariance blocks (s, j) of the last A K assembly
         # Row form (plan.Route.family "rows", rowform.py): statically possible; whether a step takes it is decided when the operators
         # are built (lattice survey, even stencils).  Column form from 4 ranks: row-sharded transforms + one all-to-all of A K block
         # columns per operator (with 2 ranks the exchange would move a quarter of A K over ONE xGMI link, more than the forward passes
@@ -233,7 +193,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self.exchange = self.route.exchange
         self._deny = {}                 # row form denied: "survey" -> (survey key, why), func -> ((survey key, B), why)
         self.step_route = None          # family the last step ran in: "rows" | "single" | "columns"
-        self._rowpath = False           # this step runs the row-sharded posterior (set by the A K assembly)
+        self._step = None               # the Step of the last posterior() (step.py); self.last["step"] once it has completed
+        self.last = None                # what the last completed posterior() left on the device
         if self.streamed and not self.use_spectral:
             raise ValueError("streamed operators feed the spectral product: needs the spectral method's grid conditions")
         # Communicator of the row exchange.  Default: the caller's own group -- collectives of one communicator run in issue order on
@@ -252,19 +213,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             ranks = torch.distributed.get_process_group_ranks(group) if group is not None else list(range(torch.distributed.get_world_size()))
             if len(ranks) == world:
                 self._xgroup = _exchange_group(tuple(ranks), torch.distributed.get_backend(group))
-        self._Arows, self._Aedge, self._fullrows, self._rowsrc, self._op_args = {}, {}, {}, {}, {}
+        self._Arows, self._Aedge, self._rowsrc, self._op_args = {}, {}, {}, {}
         self._slab_ops = set()      # data pointers of operators that hold only this rank's column slab
         self._potrf_ctx = None
         # one-rank runs issue no collective; bench.py --gpus 1 --check and the RCCL test set this so that the row form's all-gather,
         # all-reduce and agreement go through the backend with one rank (sharding._live)
         self.force_collectives = os.environ.get("GEOBO_FORCE_COLLECTIVES", "0") == "1"
         self.kernel_events = None  # set to [] to record (name, flops, start, stop) HIP events per fused launch
-        # log-likelihood gradient (logl_grad): covariance provider of a derivative Gram (None: the covariance itself), workspace
-        # renames that keep its A K / Gram apart from the step's own, no noise diagonal, and the K copy a step leaves for it
-        self._dprov = None
-        self._ws_alias = None
-        self._grad_gram = False
-        self._keep_signal = False
         self.aka_hook = None       # callable(AkA) run between the assembly of AkA and its factorisation (emulation tool only)
 
     # ---- geometry --------------------------------------------------------------------------------------------
@@ -301,14 +256,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         xe, ye, ze = self.node_axes() if axes is None else axes
         # survey on the cube's own x-y lattice (the reference's workflow): translation-invariant stencil, ~2000x fewer potentials
         # (the lattice analysis is always attempted; a survey off the lattice gets plan = None)
-        pkey = (loc.tobytes(), xe.tobytes(), ye.tobytes(), ze.tobytes())
-        if self._lattice_plan is None or self._lattice_plan[0] != pkey:
-            self._lattice_plan = (pkey, hip.lattice_plan(loc, xe, ye, ze, self.nx, self.ny, self.nz, self.device))
+        skey = (loc.tobytes(), xe.tobytes(), ye.tobytes(), ze.tobytes())
+        if self._lattice_plan is None or self._lattice_plan[0] != skey:
+            self._lattice_plan = (skey, hip.lattice_plan(loc, xe, ye, ze, self.nx, self.ny, self.nz, self.device))
         plan = self._lattice_plan[1]
         # row form (rowform.py): this rank's sensor rows + the two boundary slabs of every sensor, nothing sharded by voxel columns.
         # Needs a row-major lattice survey and even stencils; a denial holds for exactly the survey / field it was found for.
         Bkey = None if B is None else tuple(np.asarray(B, dtype=float))
-        skey = (loc.tobytes(), xe.tobytes(), ye.tobytes(), ze.tobytes())
         if self._deny.get("survey", (skey,))[0] != skey:
             self._allow_rows("survey")
         if self._deny.get(func, ((skey, Bkey),))[0] != (skey, Bkey):
@@ -378,10 +332,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                     # "auto" and the stencil is not even (no lattice Gram): AkA is an N-deep GEMM against the operator -- resident
                     self._auto_denied.add(dkey)
                     return self.operator(func, sensor_locations, B=B, axes=axes, full=full)
-                from .spectral import SpectralProduct
-                if self._spectral is None and self.use_spectral:
-                    self._spectral = SpectralProduct(self.nx, self.ny, self.nz, self.device, opts=self.route.opts())
-                if self.use_spectral and self._spectral.lattice_feed and not self.f32:
+                if self.use_spectral and self._spectral_product().lattice_feed and not self.f32:
                     self._timed("a_sens_" + func, 0.0, lambda: A.keep_stencil(func))
             self._lam[func] = None if lam is None else (A, lam)
             if rows_mode:
@@ -470,12 +421,9 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         if not self.route.opt("aka_lattice"):
             return False
         from .lattice_gram import LatticeGram
-        from .spectral import SpectralProduct
         if not LatticeGram.supported(self.nx, self.ny, self.nz) or self.Ms_pad != self.Ms:
             return False
-        if self._spectral is None:
-            self._spectral = SpectralProduct(self.nx, self.ny, self.nz, self.device, opts=self.route.opts())
-        return self._spectral.lattice_feed
+        return self._spectral_product().lattice_feed
 
     def _spectral_product(self):
         """The grid's SpectralProduct, its per-kernel timer following the engine's kernel_events switch."""
@@ -501,8 +449,6 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
 
     def _workspace(self, name, shape, dtype=F64):
         """Persistent uninitialised device tensor; reallocated only when the shape changes (large hipMallocs are slow)."""
-        if self._ws_alias:
-            name = self._ws_alias.get(name, name)
         t = self._ws.get(name)
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
             self._ws.pop(name, None)
@@ -513,13 +459,9 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         """Device vector -> host array through a persistent PINNED staging buffer (valid until the next call with the same slot).
         A pageable device-to-host copy pins its destination on the fly; on a busy host that now and then took 20-30 ms for the
         4 MB of a result vector (one 64^3 step in five came out 4 % slow)."""
-        n = t.numel()
-        buf = self._host.get(slot)
-        if buf is None or buf.numel() < n or buf.dtype != t.dtype:
-            buf = self._host[slot] = torch.empty(max(n, 1), dtype=t.dtype, pin_memory=True)
-        buf[:n].copy_(t.detach().reshape(-1), non_blocking=True)
+        h = self._to_host_async(t, slot)
         torch.cuda.current_stream(self.device).synchronize()
-        return buf[:n].numpy()
+        return h
 
     def _to_host_async(self, t, slot=0):
         """Queue the copy of _to_host without waiting for it: the returned array is valid after the caller's next synchronize of the
@@ -550,36 +492,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
 
     def _op_rows_buffer(self):
         """Row-batch buffer of the streamed operators: one size for every user (no reallocation between stages)."""
-        if self._spectral is None:
-            from .spectral import SpectralProduct
-            self._spectral = SpectralProduct(self.nx, self.ny, self.nz, self.device, opts=self.route.opts())
-        return self._workspace2d("op_rows", max(256, self._spectral.R), self.N_pad)
+        return self._workspace2d("op_rows", max(256, self._spectral_product().R), self.N_pad)
 
     def _cov_table(self, kid, lj, ls, w, amp):
         """Lattice table of one covariance block; rounded through fp32 in the fp32-assembly mode."""
         sset = self.s
         tab = hip.cov_table(kid, self.nx, self.ny, self.nz, sset.xvoxsize, sset.yvoxsize, sset.zvoxsize, lj, ls, w, amp, self.device)
         return hip.round_f32_(tab) if self.f32 else tab
-
-    def _block_table(self, name, i, j, lengths, W, amp):
-        """Lattice table of covariance block (row property i, column property j) = w_ij k2(l_j, l_i) (kernels.py:183-195), or, while a
-        derivative provider is set (logl_grad), the table of that block's derivative."""
-        if self._dprov is not None:
-            return self._dprov.table(self, name, i, j, lengths, W, amp)
-        return self._cov_table(hip.kernel_id(name, i != j), lengths[j], lengths[i], W[i][j], amp)
-
-    def _k_block(self, name, i, j, rows, cols, lengths, W, amp, out):
-        """Block (i, j) of create_cov evaluated from coordinates (geobo_k_block), through the derivative provider when one is set."""
-        if self._dprov is not None:
-            return self._dprov.k_block(self, name, i, j, rows, cols, lengths, W, amp, out)
-        return hip.k_block(hip.kernel_id(name, i != j), rows, cols, lengths[j], lengths[i], W[i][j], amp, out)
-
-    def _ak_fused_block(self, name, s_, j, A, xyz, nc, lengths, W, amp, out):
-        """A_s K_sj with the covariance generated inside the fused product (coordinate route), through the derivative provider when
-        one is set."""
-        if self._dprov is not None:
-            return self._dprov.ak_fused(self, name, s_, j, A, xyz, nc, lengths, W, amp, out)
-        return hip.ak_fused(hip.kernel_id(name, s_ != j), A, xyz, self.c0, nc, lengths[j], lengths[s_], W[s_][j], amp, out)
 
     @_on_device
     def apply_operator(self, A, v):
@@ -610,9 +529,11 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         """Give the device memory back (workspaces, transform buffers, operators, eigen-data); the engine rebuilds what the next
         step needs.  bench.py --check: the ranks free their share before rank 0 runs the 1-rank comparison on the same device."""
         self.clear_operators()
-        self._ws, self._spectral, self._gram, self._gens, self._fullrows = {}, None, None, {}, {}
+        self._ws, self._spectral, self._gram = {}, None, None
         self._xyz = None
         self.last = None
+        if self._step is not None:       # (which form the step took stays readable: _rowpath)
+            self._step.gens, self._step.fullrows = {}, {}
         torch.cuda.empty_cache()
 
     # ---- stages ------------------------------------------------------------------------------------------------
@@ -625,32 +546,40 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             self.timings[name] = self.timings.get(name, 0.0) + (now - t0)
         return now
 
-    def _assemble_AK(self, A_g, A_m, sel_t, lengths, W, name, amp, props, sym=False):
-        """A K.  sym (posterior() sets it when the step will run in the transposed order on a lattice survey): only the blocks AkA's
+    @property
+    def _rowpath(self):
+        """The last posterior() step ran (or, after a failure, was going to run) the row-sharded form."""
+        return self._step is not None and self._step.rowpath
+
+    def _new_step(self, prior, props, sel_t, noise, **kw):
+        """A Step over the drill voxels sel_t (int64 device tensor or None); kw: the remaining fields of step.Step."""
+        Md = 0 if sel_t is None else sel_t.numel()
+        return Step(prior, tuple(props), sel_t, Md, hip.pad_m(2 * self.Ms_pad + Md), noise, **kw)
+
+    def _assemble_AK(self, step, A_g, A_m):
+        """A K into the workspace step.ak_slot, or None in the row form (decided here: step.rowpath), which has no A K.
+        step.sym (posterior() sets it when the step will run in the transposed order on a lattice survey): only the blocks AkA's
         LOWER triangle needs -- (grav rows, blocks 0 and 1), (magn rows, block 1), the drill rows; AkA[magn rows, grav columns] is the
         transpose of AkA[grav rows, magn columns], and nothing but AkA reads A K in that order (_mean_rows, _posterior_zpath)."""
-        self._ak_sym = bool(sym)
-        self._W = W
         xyz = self.grid_points()
-        Md = 0 if sel_t is None else sel_t.numel()
+        props, sel_t, Md, M_pad = step.props, step.sel_t, step.Md, step.M_pad
         off_d = 2 * self.Ms_pad
-        M_pad = hip.pad_m(off_d + Md)
         nc = self.nc
-        self._rowpath = False
+        step.rowpath = False
         if self.rows_static:
             self._spectral_product()
             if self._rows_agree(self._rows_ok(A_g, A_m)):
                 # row form: no column shard of A K exists (and none is allocated) -- AkA comes straight from chunks of the rank's rows
                 self._finish_exchange()  # (an exchange left over by a call that failed between its start and its factorisation)
-                self._rowpath = True
-                self._fullrows = {}
-                return None, M_pad
+                step.rowpath = True
+                step.fullrows = {}
+                return None
         # what THIS step would materialise (its own property count and element size; the planner's figure is for two blocks)
         ak_bytes = M_pad * len(props) * nc * (4 if self.f32 else 8)
         if ak_bytes > COLUMN_FORM_MAX_BYTES and self.use_spectral:
             raise RuntimeError("A K of this grid would take %.0f GB on this rank and only the row form avoids it (%s)"
                                % (ak_bytes / 1e9, self.route.note or "GEOBO_ROWS=0 / GEOBO_POSTERIOR=dense switch it off"))
-        AK = self._workspace2d("AK", M_pad, len(props) * nc, dtype=hip.F32 if self.f32 else F64)
+        AK = self._workspace2d(step.ak_slot, M_pad, len(props) * nc, dtype=hip.F32 if self.f32 else F64)
         # every sensor/drill row is overwritten below; only the padding must be defined: rows behind each row block
         # (zero, so that AkA / V get zero rows) and voxel columns >= N of the last shard (finite: they meet zero A columns)
         for r0, r1 in ((self.Ms, self.Ms_pad), (self.Ms_pad + self.Ms, off_d), (off_d + Md, M_pad)):
@@ -660,7 +589,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             for jj in range(len(props)):
                 AK[:, jj * nc + max(self.N - self.c0, 0):(jj + 1) * nc].zero_()
         if self.use_spectral:
-            self._assemble_AK_spectral(AK, A_g, A_m, lengths, W, name, amp, props, sym)
+            self._assemble_AK_spectral(step, AK, A_g, A_m)
         for jj, j in enumerate(props):
             cols = slice(jj * nc, (jj + 1) * nc)
             for s_, A in ((0, A_g), (1, A_m)):
@@ -671,22 +600,22 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                 out64 = out if not self.f32 else self._workspace2d("ak_block64", self.Ms_pad, nc)
                 if self.use_grid:
                     # regular grid: covariance = table on the index-difference lattice (built once per block, N doubles)
-                    tab = self._block_table(name, s_, j, lengths, W, amp)
+                    tab = step.prior.table(self, s_, j)
                     self._timed("ak_fused_grid", 2.0 * self.Ms_pad * self.N_pad * nc,
                                 lambda: hip.ak_fused_grid(A, self.nx, self.ny, self.nz, tab, self.c0, nc, out64),
                                 alg=2.0 * self.Ms * self.N * min(nc, max(self.N - self.c0, 0)))
                 else:
                     self._timed("ak_fused", 2.0 * self.Ms_pad * self.N_pad * nc,
-                                lambda: self._ak_fused_block(name, s_, j, A, xyz, nc, lengths, W, amp, out64),
+                                lambda: step.prior.ak_fused(self, s_, j, A, xyz, nc, out64),
                                 alg=2.0 * self.Ms * self.N * min(nc, max(self.N - self.c0, 0)))
                 if self.f32:
                     hip.convert(out64, out)
             if Md:
-                self._cov_rows(name, 2, j, lengths, W, amp, sel_t, self.c0, AK[off_d:off_d + Md, cols])
-        return AK, M_pad
+                self._cov_rows(step.prior, 2, j, sel_t, self.c0, AK[off_d:off_d + Md, cols])
+        return AK
 
-    def _cov_rows(self, name, i, j, lengths, W, amp, rows_t, col0, out):
-        """out[r, c] = block (i, j) of create_cov (kernels.py:183-195: w_ij k2(l_j, l_i)) for the row voxels rows_t (flat indices,
+    def _cov_rows(self, prior, i, j, rows_t, col0, out):
+        """out[r, c] = block (i, j) of the prior (create_cov, kernels.py:183-195: w_ij k2(l_j, l_i)) for the row voxels rows_t (flat indices,
         int64 device tensor) and the voxel columns col0 .. col0 + out.shape[1]: materialised covariance assembly.  On the regular
         grid a gather from the block's difference-lattice table (geobo_k_block_grid: bound by the HBM store), otherwise evaluated
         from coordinates (geobo_k_block)."""
@@ -694,26 +623,26 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         if ncv <= 0:
             return out
         if self.use_grid and col0 % 2 == 0:
-            tab = self._block_table(name, i, j, lengths, W, amp)
+            tab = prior.table(self, i, j)
             return hip.k_block_grid(tab, self.nx, self.ny, self.nz, rows_t, col0, out[:, :ncv])
         xyz = self.grid_points()
         rows = tuple(c[rows_t] for c in xyz)
         colc = tuple(c[col0:col0 + out.shape[1]] for c in xyz)
-        return self._k_block(name, i, j, rows, colc, lengths, W, amp, out)
+        return prior.k_block(self, i, j, rows, colc, out)
 
-    def _assemble_AK_spectral(self, AK, A_g, A_m, lengths, W, name, amp, props, sym=False):
+    def _assemble_AK_spectral(self, step, AK, A_g, A_m):
         """Sensor rows of AK through the real-DFT route (geobo_amd/spectral.py): same product, ~200x fewer flops."""
-        sp, sset, nc = self._spectral_product(), self.s, self.nc
+        sp, nc, props = self._spectral_product(), self.nc, step.props
         plane = self.nx * self.nz
         y0, y1 = self.c0 // plane, self.c1 // plane
         if self.exchange:
-            return self._assemble_AK_spectral_exchange(AK, lengths, W, name, amp, props)
+            return self._assemble_AK_spectral_exchange(step, AK)
         for s_, A in ((0, A_g), (1, A_m)):
             lams, outs = [], []
             for jj, j in enumerate(props):
-                gen = sp.eigenvalues(self._block_table(name, s_, j, lengths, W, amp))
-                self._gens[(s_, j)] = gen               # (the transposed posterior path applies the same blocks to L^-1 A_s)
-                if sym and (s_, j) not in ((0, 0), (0, 1), (1, 1)):
+                gen = sp.eigenvalues(step.prior.table(self, s_, j))
+                step.gens[(s_, j)] = gen                # (the transposed posterior path applies the same blocks to L^-1 A_s)
+                if step.sym and (s_, j) not in ((0, 0), (0, 1), (1, 1)):
                     continue
                 lams.append(gen)
                 outs.append(AK[s_ * self.Ms_pad:s_ * self.Ms_pad + self.Ms, jj * nc:(jj + 1) * nc])
@@ -769,24 +698,21 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             form = lattice_gram_form(self.exchange, self.f32 or self.streamed, self.world, self.Ms, self.c0, self.c1, plane, self.N)
             if form is None:
                 return None
-        if self._spectral is None:
-            from .spectral import SpectralProduct
-            self._spectral = SpectralProduct(self.nx, self.ny, self.nz, self.device, opts=self.route.opts())
         if self._gram is None:
-            self._gram = LatticeGram(self._spectral, self.device)
+            self._gram = LatticeGram(self._spectral_product(), self.device)
         return self._timed("aka_lattice_eigen", 0.0, lambda: self._gram.eigen(hip.a_sens_lattice_stencil(lws, self.nx, self.ny, self.nz)))
 
-    def _assemble_AkA(self, AK, M_pad, A_g, A_m, sel_t, lengths, name, amp, gp_sigma, props):
-        xyz = self.grid_points()
+    def _assemble_AkA(self, step, AK, A_g, A_m):
+        """AkA = A K A3^T (+ the noise variances) into the workspace step.aka_slot, from what _assemble_AK(step, ...) left."""
         nc = self.nc
-        Md = 0 if sel_t is None else sel_t.numel()
+        props, Md, M_pad = step.props, step.Md, step.M_pad
         off_d = 2 * self.Ms_pad
-        AkA = self._workspace("AkA", (M_pad, M_pad))
+        AkA = self._workspace(step.aka_slot, (M_pad, M_pad))
         AkA.zero_()
-        if self._rowpath or (self._row_gram() and self._fullrows):
-            return self._assemble_AkA_rows(AkA, M_pad, sel_t, lengths, name, amp, gp_sigma, props)
-        if getattr(self, "_ak_sym", False):
-            return self._assemble_AkA_sym(AkA, AK, M_pad, A_g, A_m, sel_t, lengths, name, amp, gp_sigma, props)
+        if step.rowpath or (self._row_gram() and step.fullrows):
+            return self._assemble_AkA_rows(step, AkA)
+        if step.sym:
+            return self._assemble_AkA_sym(step, AkA, AK, A_g, A_m)
         # only the LOWER triangle of AkA is consumed (Cholesky, lower=True): block column s needs rows >= s*Ms_pad, and
         # tiles strictly above the diagonal are skipped inside the GEMM (47 % fewer tiles at 64^3)
         for s_, A in ((0, A_g), (1, A_m)):
@@ -865,30 +791,29 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             else:
                 self._timed("aka_gemm_nt", fl, lambda: hip.gemm_nt(Xv, Yv, Cv, lower_only=True, m_valid=mv), alg=alg)
         allreduce_sum_(AkA, self.world, self.group)
-        return self._finish_AkA(AkA, M_pad, sel_t, lengths, name, amp, gp_sigma)
+        return self._finish_AkA(step, AkA)
 
-    def _finish_AkA(self, AkA, M_pad, sel_t, lengths, name, amp, gp_sigma):
+    def _finish_AkA(self, step, AkA):
         """Drill columns by symmetry, the drill-drill block, the noise variances on the diagonal (identity on the padding).
-        A derivative Gram (logl_grad) gets neither: its padding stays zero.  _keep_signal: the matrix before the diagonal is copied
-        into the "K_signal" workspace (the signal part of K, for the amplitude and weight derivatives)."""
+        A derivative Gram (step.noise None) gets no diagonal: its padding stays zero.  step.keep_signal: the matrix before the diagonal
+        is copied into the "K_signal" workspace (the signal part of K, for the amplitude and weight derivatives)."""
         xyz = self.grid_points()
-        Md = 0 if sel_t is None else sel_t.numel()
+        sel_t, Md, gp_sigma = step.sel_t, step.Md, step.noise
         off_d = 2 * self.Ms_pad
-        if not self._grad_gram:
-            dvec = torch.ones(M_pad, dtype=F64, device=self.device)
+        if gp_sigma is not None:
+            dvec = torch.ones(step.M_pad, dtype=F64, device=self.device)
             dvec[0:self.Ms] = float(gp_sigma[0]) ** 2
             dvec[self.Ms_pad:self.Ms_pad + self.Ms] = float(gp_sigma[1]) ** 2
         if Md:
             AkA[:off_d, off_d:off_d + Md] = AkA[off_d:off_d + Md, :off_d].t()
             rows = tuple(c[sel_t] for c in xyz)
-            # (create_cov's self blocks carry weight 1; a derivative Gram's weight matrix may have 0 there: the unit-weight pair Gram)
-            W = self._W if self._grad_gram else [[1.0] * 3] * 3
-            self._k_block(name, 2, 2, rows, rows, lengths, W, amp, AkA[off_d:off_d + Md, off_d:off_d + Md])
-            if not self._grad_gram:
+            # (create_cov's self blocks carry weight 1: weight_matrix; the unit-weight pair Gram of logl_grad has 0 there)
+            step.prior.k_block(self, 2, 2, rows, rows, AkA[off_d:off_d + Md, off_d:off_d + Md])
+            if gp_sigma is not None:
                 dvec[off_d:off_d + Md] = float(gp_sigma[2]) ** 2
-        if self._grad_gram:
+        if gp_sigma is None:
             return AkA
-        if self._keep_signal:
+        if step.keep_signal:
             self._workspace("K_signal", tuple(AkA.shape)).copy_(AkA)
         AkA.diagonal().add_(dvec)
         return AkA
@@ -925,18 +850,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         Returns dict(mu (3N, NaN for skipped property blocks), var, logl, info).
         keep_K (internal, logl_grad): keep a copy of the assembled K without its diagonal (workspace "K_signal") before the
         in-place factorisation."""
-        self._keep_signal = bool(keep_K)
-        try:
-            return self._posterior(A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, props, calclogl,
-                                   want_mean_var)
-        finally:
-            self._keep_signal = False
-
-    def _posterior(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, props, calclogl,
-                   want_mean_var):
         props = tuple(props)
         assert 0 in props and 1 in props, "gravity and magnetic blocks are needed for AkA"
-        W = self._W = weight_matrix(crossweights)
         sel = np.asarray(sel, dtype=np.int64)
         sel_t = torch.as_tensor(sel, device=self.device) if sel.size else None
         t = self._tick("start")
@@ -945,11 +860,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         if self.rows_static and not self._rows_denied and not self._rows_ok(A_g, A_m) and all(f in self._op_args for f in ("grav", "magn")):
             # operators handed in from before a denial / a clear: rebuild them from the recorded arguments in the form this step takes
             A_g, A_m = (self.operator(f, *self._op_args[f][:1], B=self._op_args[f][1], axes=self._op_args[f][2]) for f in ("grav", "magn"))
-        AK, M_pad = self._assemble_AK(A_g, A_m, sel_t, lengths, W, kernelfunc, gp_amp, props,
-                                      sym=not self.rows_static and self._sym_ok(A_g, A_m))
-        self.step_route = "rows" if self._rowpath else ("single" if self._ak_sym else "columns")
+        step = self._step = self._new_step(Prior(kernelfunc, lengths, weight_matrix(crossweights), gp_amp), props, sel_t, gp_sigma,
+                                           keep_signal=bool(keep_K), sym=not self.rows_static and self._sym_ok(A_g, A_m))
+        M_pad = step.M_pad
+        AK = self._assemble_AK(step, A_g, A_m)
+        self.step_route = "rows" if step.rowpath else ("single" if step.sym else "columns")
         t = self._tick("ak_fused", t)
-        AkA = self._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, lengths, kernelfunc, gp_amp, gp_sigma, props)
+        AkA = self._assemble_AkA(step, AK, A_g, A_m)
         if self.aka_hook is not None:          # tools/emulate_rank.py: keep the assembled matrix (1 rank) / put the true one in place
             self.aka_hook(AkA)                 # of what an emulated all-gather produced (a lone rank of G)
         t = self._tick("aka", t)
@@ -994,8 +911,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                 out["logl"] = 0.0
         if not want_mean_var:
             check_factor()
-        if want_mean_var and self._rowpath:
-            mu_f, var_f = self._posterior_rows(Linv, u, sel_t, lengths, W, kernelfunc, gp_amp, props, M_pad)
+        if want_mean_var and step.rowpath:
+            mu_f, var_f = self._posterior_rows(step, Linv, u)
             N_ = len(props) * self.N
             hq = self._to_host_async(torch.cat([mu_f.reshape(-1)[:N_], var_f.reshape(-1)[:N_]]), 0)
             check_factor()
@@ -1009,11 +926,11 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             fl = 2.0 * AK.shape[1] * sum(64.0 * 64 * g + 2560.0 for g in range((Mv + 63) // 64))
             Mu = 2 * self.Ms + len(sel)                                  # unpadded observation rows
             nv = len(props) * min(self.nc, max(self.N - self.c0, 0))     # this rank's voxel-property columns
-            zp = self._zpath_ok(AK, props, A_g, A_m)
-            if self._ak_sym and not zp:
+            zp = self._zpath_ok(step, AK)
+            if step.sym and not zp:
                 raise RuntimeError("internal: A K was assembled for the transposed posterior, which is not available")
             if zp:
-                mu_l, var_l = self._posterior_zpath(Linv, AK, u, A_g, A_m, sel_t, lengths, W, kernelfunc, gp_amp, props, M_pad)
+                mu_l, var_l = self._posterior_zpath(step, Linv, AK, u, A_g, A_m)
             elif AK.dtype == F64:
                 mu_l, var_l = self._timed("posterior_reduce", fl, lambda: hip.posterior_reduce(
                     Linv, AK, u, gp_amp * 1.0, self._workspace("post_ws", (hip.posterior_ws_doubles(M_pad, AK.shape[1]),)), m_valid=Mv),
@@ -1044,26 +961,18 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             self._tick("d2h", t)
         # A K is published only when it is whole; the symmetric plan leaves the blocks (magn rows, block 0) and (sensor rows, block 2)
         # unwritten: that buffer goes under AK_partial (the tests' oracle contacts read its assembled blocks); the row form has none
-        whole = AK is not None and not self._ak_sym
+        whole = AK is not None and not step.sym
         self.last = dict(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props, sel=sel,
-                         ops=(A_g, A_m))
+                         ops=(A_g, A_m), step=step)
         return out
 
-    def _derivative_gram(self, A_g, A_m, sel_t, lengths, W, name, amp, props, provider, slot):
+    def _derivative_gram(self, A_g, A_m, sel_t, prior, slot):
         """A derivative Gram dK in workspace `slot`: posterior()'s own assembly (_assemble_AK / _assemble_AkA, whichever route the
-        step takes) fed by `provider` (None: the covariance tables themselves, here with the weight matrix W), without the noise
-        diagonal, zero padding, lower triangle valid.  A K and the Gram go to workspaces of their own, and what a later step reads
-        of this one (the block generators, the plan flags) is restored."""
-        saved = (self._gens, self._W, getattr(self, "_ak_sym", False), self._rowpath, self._fullrows)
-        self._gens = dict(self._gens)
-        self._dprov, self._ws_alias, self._grad_gram = provider, {"AK": "dK_AK", "AkA": slot}, True
-        try:
-            AK, M_pad = self._assemble_AK(A_g, A_m, sel_t, lengths, W, name, amp, props,
-                                          sym=not self.rows_static and self._sym_ok(A_g, A_m))
-            return self._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, lengths, name, amp, None, props)
-        finally:
-            self._dprov, self._ws_alias, self._grad_gram = None, None, False
-            self._gens, self._W, self._ak_sym, self._rowpath, self._fullrows = saved
+        step takes) as a step of its own over `prior`, without the noise diagonal, zero padding, lower triangle valid.  Its A K and
+        its Gram go to workspaces of their own; the step the factor came from (self.last) is not touched."""
+        step = self._new_step(prior, (0, 1, 2), sel_t, None, ak_slot="dK_AK", aka_slot=slot,
+                              sym=not self.rows_static and self._sym_ok(A_g, A_m))
+        return self._assemble_AkA(step, self._assemble_AK(step, A_g, A_m), A_g, A_m)
 
     @_on_device
     def logl_grad(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, directions):
@@ -1099,8 +1008,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             for (a, b), w in zip(WEIGHT_PAIRS, wvals):
                 if w == 0.0:
                     Wu[a][b] = Wu[b][a] = 1.0
-            G0.add_(self._derivative_gram(A_g, A_m, sel_t, lengths, Wu, kernelfunc, gp_amp, props, None, "dK_unit"))
-        Gs = [G0] + [self._derivative_gram(A_g, A_m, sel_t, lengths, W, kernelfunc, gp_amp, props, DirectionalCov(d), "dK_dir%d" % t)
+            G0.add_(self._derivative_gram(A_g, A_m, sel_t, Prior(kernelfunc, lengths, Wu, gp_amp), "dK_unit"))
+        Gs = [G0] + [self._derivative_gram(A_g, A_m, sel_t, Prior(kernelfunc, lengths, W, gp_amp, deriv=d), "dK_dir%d" % t)
                      for t, d in enumerate(directions)]
         segs = ((0, self.Ms), (self.Ms_pad, self.Ms_pad + self.Ms), (2 * self.Ms_pad, 2 * self.Ms_pad + len(sel)))
         out = self._timed("kinv_dot", M_pad ** 3 / 3.0, lambda: hip.kinv_dot(

@@ -37,10 +37,11 @@ def _vertical_bases(idx, nz):
 
 
 class SetStatisticsMixin:
-    def _set_sampler(self, name, lengths, W, amp):
+    def _set_sampler(self, prior):
         """PriorSampler whose exact circulant product applies K (generic source), cached per hyper-parameters."""
         from .sampling import PriorSampler
         s = self.s
+        name, lengths, W, amp = prior.name, prior.lengths, prior.W, prior.amp
         key = (name, tuple(float(v) for v in lengths), tuple(map(tuple, W)), float(amp))
         hit = getattr(self, "_set_smp", None)
         if hit is None or hit[0] != key:
@@ -49,16 +50,17 @@ class SetStatisticsMixin:
             hit = self._set_smp = (key, smp)
         return hit[1]
 
-    def _vd_spectral(self, Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m):
-        """Tiles (V, n) of 128 rows of V_d on the transposed route, voxel order (iy, ix, iz)."""
+    def _vd_spectral(self, step, prior, Linv, A_g, A_m):
+        """Tiles (V, n) of 128 rows of V_d on the transposed route, voxel order (iy, ix, iz): the generators of the step whose factor
+        Linv is, the drill block's from `prior`."""
+        sel_t, Md = step.sel_t, step.Md
         sp, N, Msp, T = self._spectral, self.N, self.Ms_pad, 128
         lat = (self._gram is not None and self._gram.edge_supported() and Msp == self.nx * self.ny and self.route.opt("z_lattice")
                and all(self._lam.get(f) is not None and self._lam[f][0] is A for f, A in (("grav", A_g), ("magn", A_m))))
         if not lat:
             Ag = self._resident_operator(A_g, "grav")
             Am = self._resident_operator(A_m, "magn")
-        gens = [self._gens[(0, 2)], self._gens[(1, 2)],
-                sp.eigenvalues(self._cov_table(hip.kernel_id(name, False), lengths[2], lengths[2], W[2][2], amp))]
+        gens = [step.gens[(0, 2)], step.gens[(1, 2)], sp.eigenvalues(prior.table(self, 2, 2))]
         Zg, Zm, Zd, V, tmp = (self._workspace2d(nm, T, N) for nm in ("set_Zg", "set_Zm", "set_Zd", "set_V", "set_Vt"))
         Mv = 2 * Msp + Md
         for b0 in range(0, Mv, T):
@@ -82,8 +84,9 @@ class SetStatisticsMixin:
                 V[:n].add_(tmp[:n])
             yield V, n
 
-    def _vd_generic(self, Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m, AK):
+    def _vd_generic(self, step, prior, Linv, A_g, A_m, AK):
         """Tiles (V, n) of 256 rows of V_d on any one-rank fp64 step, voxel order (iy, ix, iz)."""
+        sel_t, Md = step.sel_t, step.Md
         N, Np, Msp, T = self.N, self.N_pad, self.Ms_pad, 256
         Mv = 2 * Msp + Md
         if AK is not None:
@@ -95,7 +98,7 @@ class SetStatisticsMixin:
                 hip.gemm_nn(Linv[b0:e, :e], AKd[:e], V)
                 yield V, min(T, Mv - b0)
             return
-        smp = self._set_sampler(name, lengths, W, amp)
+        smp = self._set_sampler(prior)
         Zt = torch.empty((T, 3, N), dtype=F64, device=self.device)
         Zp = self._workspace2d("set_Zp", T, Np)
         for b0 in range(0, Mv, T):
@@ -122,6 +125,7 @@ class SetStatisticsMixin:
         Returns device tensors (info_gain, path_var, sum_var, status), C each; status 1 + pivot marks a set whose S did not factorise
         (NaN outputs).  One rank, fp64 assembly, a step over property blocks (0, 1, 2)."""
         from .engine import weight_matrix
+        from .step import Prior
         if self.world > 1:
             raise NotImplementedError("set statistics run on one rank (world = %d)" % self.world)
         last = self.last
@@ -136,21 +140,18 @@ class SetStatisticsMixin:
         if np.any(sets >= self.N):
             raise ValueError("set entries must be flat voxel indices below N = %d (negative: padding)" % self.N)
         with torch.cuda.device(self.device):
-            return self._set_statistics(sets.astype(np.int64), kernelfunc, lengths, weight_matrix(crossweights), float(gp_amp),
+            return self._set_statistics(sets.astype(np.int64), Prior(kernelfunc, lengths, weight_matrix(crossweights), float(gp_amp)),
                                         float(gp_sigma[2]) ** 2, observed, source, AK)
 
-    def _set_statistics(self, sets, name, lengths, W, amp, sigma2, observed, source, AK):
+    def _set_statistics(self, sets, prior, sigma2, observed, source, AK):
         last = self.last
-        Linv = last["Linv"]
+        Linv, step = last["Linv"], last["step"]
         A_g, A_m = last["ops"]
-        sel = np.asarray(last["sel"], dtype=np.int64)
-        Md = len(sel)
-        sel_t = torch.as_tensor(sel, device=self.device) if Md else None
         C_, k = sets.shape
         dev = self.device
         idx = torch.as_tensor(sets.astype(np.int32), device=dev)
         G = torch.zeros((C_, k, k), dtype=F64, device=dev)
-        spectral_ok = self._zpath_ok(AK, (0, 1, 2), A_g, A_m)
+        spectral_ok = self._zpath_ok(step, AK)
         if source == "auto":
             source = "spectral" if spectral_ok else "generic"
         if source == "spectral" and not spectral_ok:
@@ -159,9 +160,9 @@ class SetStatisticsMixin:
             raise ValueError("source must be 'auto', 'spectral' or 'generic'")
         self.set_source = source
         if source == "spectral":
-            tiles = self._vd_spectral(Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m)
+            tiles = self._vd_spectral(step, prior, Linv, A_g, A_m)
         else:
-            tiles = self._vd_generic(Linv, sel_t, Md, lengths, W, name, amp, A_g, A_m, AK if last["AK_complete"] else None)
+            tiles = self._vd_generic(step, prior, Linv, A_g, A_m, AK if last["AK_complete"] else None)
 
         def sweep():
             first = True
@@ -171,18 +172,17 @@ class SetStatisticsMixin:
         self._timed("set_sweep", 0.0, sweep)
         # prior block K_dd(P, P): one block for whole z-columns (the prior is stationary), else one per set
         xyz = self.grid_points()
-        kid = hip.kernel_id(name, False)
         base = _vertical_bases(sets, self.nz)
         if base is not None:
             col = torch.as_tensor(np.arange(k) + int(base[0]) if C_ else np.arange(k), device=dev)
             Kpp = torch.empty((k, k), dtype=F64, device=dev)
-            hip.k_block(kid, tuple(c[col] for c in xyz), tuple(c[col] for c in xyz), lengths[2], lengths[2], W[2][2], amp, Kpp)
+            prior.k_block(self, 2, 2, tuple(c[col] for c in xyz), tuple(c[col] for c in xyz), Kpp)
         else:
             Kpp = torch.empty((C_, k, k), dtype=F64, device=dev)
             pts = torch.as_tensor(np.maximum(sets, 0), device=dev)
             for c in range(C_):
                 p = tuple(x[pts[c]] for x in xyz)
-                hip.k_block(kid, p, p, lengths[2], lengths[2], W[2][2], amp, Kpp[c])
+                prior.k_block(self, 2, 2, p, p, Kpp[c])
         obs = None
         if observed is not None:
             obs = torch.as_tensor(np.asarray(observed, dtype=bool).reshape(-1)[:self.N].astype(np.uint8), device=dev)

@@ -80,18 +80,18 @@ class RowFormMixin:
         for k, iy in enumerate((0, self.ny - 1)):
             gram.edge_rows(X[:, iy * pl:], nrows, self._edge_spectrum(func, k, self._Aedge[func][k]), out)
 
-    def _rows_aka_local(self, props, sel_t, lengths, W, name, amp):
+    def _rows_aka_local(self, step):
         """Row blocks of AkA this rank owns: (rows_r, 3 Ms_pad) = its gravity rows against grav | magn columns and its magnetic rows
         against magn columns, and the drill rows (every rank computes those few rows itself: cheaper than shipping them).  The rank's
         rows of A K exist a chunk at a time only."""
         sp, G, Msp = self._spectral, self.world, self.Ms_pad
-        rows_r, Md = self.Ms // G, 0 if sel_t is None else sel_t.numel()
+        rows_r, Md = self.Ms // G, step.Md
         g_first = self.rank * rows_r
         loc = self._workspace("aka_rows_local", (rows_r, 3 * Msp))
         loc.zero_()
         ck = min(self._rows_chunk(2), (rows_r + sp.R - 1) // sp.R * sp.R)
         X = [self._workspace2d("rows_ak_%d" % i, ck, self.N_pad) for i in range(2)]
-        pre = self._fullrows if (self._fullrows and not self._rowpath) else None
+        pre = step.fullrows if (step.fullrows and not step.rowpath) else None
         for s_, func, blocks in ((0, "grav", ((0, 0), (1, 1))), (1, "magn", ((1, 2),))):       # (column block j, slot k of loc)
             if pre is not None:
                 # column form with the row exchange (GEOBO_POSTERIOR=dense on a lattice survey, >= 4 ranks): the rank's rows of A K were
@@ -100,10 +100,10 @@ class RowFormMixin:
                     self._timed("aka_lattice", self._gram.flops(rows_r, self.ny),
                                 lambda: self._rows_times_AT(pre[(s_, j)][:, :self.N], rows_r, j, loc[:, k * Msp:(k + 1) * Msp]))
                 continue
-            for j in props:
-                gen = sp.eigenvalues(self._block_table(name, s_, j, lengths, W, amp))
-                self._gens[(s_, j)] = gen            # (the transposed posterior applies the same blocks to L^-1 A_s)
-            lams = [self._gens[(s_, j)] for j, _ in blocks]
+            for j in step.props:
+                gen = sp.eigenvalues(step.prior.table(self, s_, j))
+                step.gens[(s_, j)] = gen             # (the transposed posterior applies the same blocks to L^-1 A_s)
+            lams = [step.gens[(s_, j)] for j, _ in blocks]
             for c0 in range(0, rows_r, ck):
                 n = min(ck, rows_r - c0)
                 outs = [X[i][:n] for i in range(len(blocks))]
@@ -122,7 +122,7 @@ class RowFormMixin:
             def drill_rows():
                 for sp_ in (0, 1):
                     Xd.zero_()
-                    self._cov_rows(name, 2, sp_, lengths, W, amp, sel_t, 0, Xd[:Md, :self.N])
+                    self._cov_rows(step.prior, 2, sp_, step.sel_t, 0, Xd[:Md, :self.N])
                     self._rows_times_AT(Xd[:, :self.N], Md, sp_, drill[:, sp_ * Msp:(sp_ + 1) * Msp])
             self._timed("aka_lattice", self._gram.flops(2 * Md, self.ny), drill_rows)
         return loc, drill
@@ -139,21 +139,22 @@ class RowFormMixin:
             AkA[off_d:off_d + Md, :off_d].copy_(drill[:Md])
         return AkA
 
-    def _assemble_AkA_rows(self, AkA, M_pad, sel_t, lengths, name, amp, gp_sigma, props):
+    def _assemble_AkA_rows(self, step, AkA):
         """AkA from row blocks: local correlation of this rank's sensor rows, one all-gather."""
-        loc, drill = self._rows_aka_local(props, sel_t, lengths, self._W, name, amp)
+        loc, drill = self._rows_aka_local(step)
         allrows = self._timed("xgmi_all_gather", 0.0, lambda: gather_rows(loc, self.world, self.group, force=self.force_collectives))
-        self._rows_aka_place(AkA, allrows, drill, sel_t)
-        return self._finish_AkA(AkA, M_pad, sel_t, lengths, name, amp, gp_sigma)
+        self._rows_aka_place(AkA, allrows, drill, step.sel_t)
+        return self._finish_AkA(step, AkA)
 
     # ---- posterior ---------------------------------------------------------------------------------------------------------------
-    def _posterior_rows(self, Linv, u, sel_t, lengths, W, name, amp, props, M_pad):
+    def _posterior_rows(self, step, Linv, u):
         """The transposed posterior (engine._posterior_zpath) sharded by ROWS of L^-1 over the ranks: rank r carries the rows of its own
         Ms / G gravity and Ms / G magnetic sensors (2 + 1 row blocks of Z = L^-1 A, a chunk at a time) and a 1/G share of the drill
         rows through the covariance product; the partial sums of squares meet in ONE all-reduce of P_c N doubles (4 MB at 64^3); the
         mean is three rows through the covariance product and every rank forms it whole (_mean_rows).
         Returns (mu, var), (P_c, N) each, complete on every rank."""
-        sp, N, Msp, P_c, Md = self._spectral, self.N, self.Ms_pad, len(props), 0 if sel_t is None else sel_t.numel()
+        props, Md, M_pad = step.props, step.Md, step.M_pad
+        sp, N, Msp, P_c = self._spectral, self.N, self.Ms_pad, len(props)
         nx, ny, nz, G, r = self.nx, self.ny, self.nz, self.world, self.rank
         rows_r = self.Ms // G
         a0, a1 = r * rows_r, Msp + r * rows_r
@@ -165,8 +166,7 @@ class RowFormMixin:
         def mean():
             # every rank forms the whole mean itself (three rows through the covariance product: cheaper than an all-reduce of it)
             w = hip.colgemv(Linv, u, ws=cws)                                   # L^-T u
-            return self._mean_rows(w, sel_t, lengths, W, name, amp, props,
-                                   lambda func, wv, out: self._lattice_Z(wv.view(1, -1), 1, func, None, out, edge=edge_of(func)))
+            return self._mean_rows(step, w, lambda func, wv, out: self._lattice_Z(wv.view(1, -1), 1, func, None, out, edge=edge_of(func)))
         mu = self._timed("posterior_mean", 0.0, mean)
         gram = self._gram
         zx = gram.zx_supported() and sp.fused_ss()           # rows of Z as [iy][iz][ix]: what the fused (row, z)-plane inverse writes
@@ -176,7 +176,7 @@ class RowFormMixin:
         ss = [self._workspace("post_ss_%d" % jj, (slots, ny, nx * nz)) for jj in range(P_c)]
         for t in ss:
             t.zero_()
-        gens_g, gens_m = [self._gens[(0, j)] for j in props], [self._gens[(1, j)] for j in props]
+        gens_g, gens_m = [step.gens[(0, j)] for j in props], [step.gens[(1, j)] for j in props]
         swap = (lambda g: g.view(ny, sp.Px, sp.Pz).transpose(1, 2).contiguous().view(-1)) if zx else (lambda g: g)
         tg, tm = [swap(g) for g in gens_g], [swap(g) for g in gens_m]
         # blocks (0, 1) and (1, 0) of a symmetric prior coincide: three y-stage products per two-term row instead of four
@@ -207,11 +207,10 @@ class RowFormMixin:
         nd = min(Md, d0 + dper) - d0
         if nd:
             def drill_rows():
-                part = self._drill_rows_ss(Linv, d0, nd, sel_t, lengths, W, name, amp, props, gens_g, gens_m,
-                                           lambda Lv, n, func, out: self._lattice_Z(Lv, n, func, None, out, edge=edge_of(func)),
-                                           None, None)
+                part = self._drill_rows_ss(step, Linv, d0, nd,
+                                           lambda Lv, n, func, out: self._lattice_Z(Lv, n, func, None, out, edge=edge_of(func)), None, None)
                 for jj in range(P_c):
                     ssq[jj].add_(part[jj])
             self._timed("posterior_drill_rows", 0.0, drill_rows)
         self._timed("xgmi_all_reduce", 0.0, lambda: allreduce_sum_(ssq, G, self.group, force=self.force_collectives))
-        return mu, amp * 1.0 - ssq
+        return mu, step.prior.amp * 1.0 - ssq

@@ -24,13 +24,13 @@ class TransposedPosteriorMixin:
         return (self._gram is not None and self._gram.edge_supported() and self.Ms_pad == self.nx * self.ny
                 and all(self._lam.get(f) is not None and self._lam[f][0] is A for f, A in (("grav", A_g), ("magn", A_m))))
 
-    def _assemble_AkA_sym(self, AkA, AK, M_pad, A_g, A_m, sel_t, lengths, name, amp, gp_sigma, props):
+    def _assemble_AkA_sym(self, step, AkA, AK, A_g, A_m):
         """AkA on one device from the blocks of A K the symmetric plan keeps, row block by row block through the lattice Gram:
         [grav rows -> grav columns], [grav rows -> magn columns] (transposed into the lower-left block, which is what the
         factorisation reads), [magn rows -> magn columns], drill rows -> both.  A quarter of the Gram's and of A K's work less than the
         block-column form, which computes the lower-left block from A_m K_10 as well."""
         gram, pl, ny, Msp, nc = self._gram, self.nx * self.nz, self.ny, self.Ms_pad, self.nc
-        Md, off_d = 0 if sel_t is None else sel_t.numel(), 2 * self.Ms_pad
+        Md, off_d, props = step.Md, 2 * self.Ms_pad, step.props
         lam = {0: self._lam["grav"][1], 1: self._lam["magn"][1]}
         ops = {0: A_g, 1: A_m}
 
@@ -55,7 +55,7 @@ class TransposedPosteriorMixin:
                 rows_times_AT(blk(off_d, 0), Md, 0, AkA[off_d:, 0:Msp])
                 rows_times_AT(blk(off_d, 1), Md, 1, AkA[off_d:, Msp:2 * Msp])
         self._timed("aka_lattice", gram.flops(3 * self.Ms + 2 * Md, ny), run)
-        return self._finish_AkA(AkA, M_pad, sel_t, lengths, name, amp, gp_sigma)
+        return self._finish_AkA(step, AkA)
 
     def _zpath_static_ok(self):
         """The one-rank transposed posterior on the fused kernels (plan.Route.single): one rank, fp64 A K, the radix-2 transform kernels
@@ -65,10 +65,10 @@ class TransposedPosteriorMixin:
         self._spectral_product()
         return True
 
-    def _zpath_ok(self, AK, props, A_g, A_m):
-        """... and the covariance generators of the last A K assembly."""
+    def _zpath_ok(self, step, AK):
+        """... and the covariance generators of the step's A K assembly."""
         return (self._zpath_static_ok() and AK is not None and AK.dtype == F64
-                and all((s_, j) in self._gens for s_ in (0, 1) for j in props))
+                and all((s_, j) in step.gens for s_ in (0, 1) for j in step.props))
 
     def _resident_operator(self, A, func):
         """A materialised copy of a forward operator that the route so far only kept implicitly (stencil table + boundary slabs)."""
@@ -106,7 +106,7 @@ class TransposedPosteriorMixin:
                 vt = self._edgeVt[key] = (ycols.data_ptr(), gram.edge_eigen_t(ycols))
             gram.edge_apply_transpose(Lview, nrows, vt[1], out[:, iy * pl:(iy + 1) * pl], zx=zx)
 
-    def _posterior_zpath(self, Linv, AK, u, A_g, A_m, sel_t, lengths, W, name, amp, props, M_pad):
+    def _posterior_zpath(self, step, Linv, AK, u, A_g, A_m):
         """Posterior mean and variance in the TRANSPOSED order (round 3).  V = L^-1 (A3 K) is (L^-1 A3) K as well, and A3 is block
         diagonal: applying L^-1 to the forward operators costs M x Ms x N per operator -- independent of the number of property blocks
         and only over the operator's own columns of L^-1 -- where applying it to A K costs M^2 / 2 x N per property block:
@@ -116,7 +116,8 @@ class TransposedPosteriorMixin:
         and the covariance products run through the same spectral kernels as A K, with the inverse transform squaring and summing
         its output planes over the rows instead of storing them (geobo_xz2d_fold_inv_ss): V is never written.  The mean needs no V
         at all: mu = (A K)^T (L^-T u), two weighted column sums.  Same arithmetic up to summation order (inversion.py:114-117)."""
-        sp, N, Msp, P_c, Md = self._spectral, self.N, self.Ms_pad, len(props), 0 if sel_t is None else sel_t.numel()
+        props, Md, M_pad, amp = step.props, step.Md, step.M_pad, step.prior.amp
+        sp, N, Msp, P_c = self._spectral, self.N, self.Ms_pad, len(props)
         nx, ny, nz = self.nx, self.ny, self.nz
         cws = self._workspace("colgemv_ws", (max(hip.colgemv_ws_doubles(M_pad, M_pad), hip.colgemv_ws_doubles(Msp, self.N_pad)),))
         w = self._timed("posterior_mean", 0.0, lambda: hip.colgemv(Linv, u, ws=cws))
@@ -149,12 +150,12 @@ class TransposedPosteriorMixin:
                 hip.gemm_nn(Linv[Msp:2 * Msp, Msp:2 * Msp], Am[:Msp, :N], Zm, x_lower=True)
             self._timed("posterior_zgemm", fl, zgemm, alg=alg)
             vec_of = lambda func, wv, out: hip.colgemv((Ag if func == "grav" else Am)[:Msp, :N], wv, out=out[0], ws=cws)
-        mu_l = self._timed("posterior_mean", 0.0, lambda: self._mean_rows(w, sel_t, lengths, W, name, amp, props, vec_of)).reshape(-1)
+        mu_l = self._timed("posterior_mean", 0.0, lambda: self._mean_rows(step, w, vec_of)).reshape(-1)
         slots = hip.xz2d_fold_inv_ss_slots(nx, sp.R, ny)
         ss = [self._workspace("post_ss_%d" % jj, (slots, ny, nx * nz)) for jj in range(P_c)]
         for t in ss:
             t.zero_()
-        gens_g, gens_m = [self._gens[(0, j)] for j in props], [self._gens[(1, j)] for j in props]
+        gens_g, gens_m = [step.gens[(0, j)] for j in props], [step.gens[(1, j)] for j in props]
         zx = lat and zx
         swap = (lambda g: g.view(ny, sp.Px, sp.Pz).transpose(1, 2).contiguous().view(-1)) if zx else (lambda g: g)   # tables of transposed planes
         tg, tm = [swap(g) for g in gens_g], [swap(g) for g in gens_m]
@@ -169,17 +170,16 @@ class TransposedPosteriorMixin:
             ssum = torch.stack([t.sum(0).reshape(-1) for t in ss])                        # (P_c, N), voxel order (iy, ix, iz)
         if Md:
             ssum = ssum + self._timed("posterior_drill_rows", 0.0, lambda: self._drill_rows_ss(
-                Linv, 0, Md, sel_t, lengths, W, name, amp, props, gens_g, gens_m,
-                (lambda Lv, n, func, out: self._lattice_Z(Lv, n, func, A_g if func == "grav" else A_m, out)) if lat else None, Ag, Am))
+                step, Linv, 0, Md, (lambda Lv, n, func, out: self._lattice_Z(Lv, n, func, A_g if func == "grav" else A_m, out)) if lat else None, Ag, Am))
         return mu_l, (amp * 1.0 - ssum).reshape(-1)
 
-    def _mean_rows(self, w, sel_t, lengths, W, name, amp, props, vec_of):
+    def _mean_rows(self, step, w, vec_of):
         """Posterior mean (P_c, N):  mu_j = (A3 K)[:, block j]^T w  re-associated as  K_.j (A3^T w)  -- the covariance blocks are
         symmetric, so three N-vectors (A_g^T w_g, A_m^T w_m, the drill weights scattered to their voxels) go through the covariance
         product as ONE row each (0.3 ms) where the weighted column sums of A K read all of it (35 GB at 64^3: 6 ms).
         vec_of(func, weights, out (1 x N)): out = A_func^T weights.  w = L^-T u (inversion.py:105,115)."""
+        props, sel_t, Md = step.props, step.sel_t, step.Md
         sp, N, Msp, P_c = self._spectral, self.N, self.Ms_pad, len(props)
-        Md = 0 if sel_t is None else sel_t.numel()
         V = self._workspace2d("mean_rows", 4, N)
         vec_of("grav", w[:Msp], V[0:1])
         vec_of("magn", w[Msp:2 * Msp], V[1:2])
@@ -191,23 +191,24 @@ class TransposedPosteriorMixin:
         mu = torch.zeros((P_c, N), dtype=F64, device=self.device)
         tmp = [self._workspace2d("mean_tmp_%d" % jj, 2, N) for jj in range(P_c)]
         for rows, s_ in terms:
-            gens = [self._gens[(s_, j)] if s_ < 2 else
-                    sp.eigenvalues(self._cov_table(hip.kernel_id(name, s_ != j), lengths[j], lengths[s_], W[s_][j], amp)) for j in props]
+            gens = [step.gens[(s_, j)] if s_ < 2 else sp.eigenvalues(step.prior.table(self, s_, j)) for j in props]
             sp.product(rows, 1, gens, tmp)
             for jj in range(P_c):
                 mu[jj].add_(tmp[jj][0])
         return mu
 
-    def _drill_rows_ss(self, Linv, d0, nd, sel_t, lengths, W, name, amp, props, gens_g, gens_m, lattice_Z, Ag, Am):
+    def _drill_rows_ss(self, step, Linv, d0, nd, lattice_Z, Ag, Am):
         """(P_c, N) sums of squares of V = L^-1 (A3 K) over the drill rows d0 .. d0 + nd of the row block behind the sensor rows:
         L^-1 is lower triangular, so only THESE rows see the drill columns.  Tiles of up to 128 rows through the storing covariance
         product, three terms (gravity, magnetic, drill block rows of K), squared and summed here.  lattice_Z(Lview, n, func, out):
         rows of L^-1 A on a lattice survey; None: MFMA GEMMs against the resident operators Ag / Am (whole 128-row tiles)."""
-        sp, N, Msp, P_c, Md, T = self._spectral, self.N, self.Ms_pad, len(props), sel_t.numel(), 128
+        props, sel_t, Md = step.props, step.sel_t, step.Md
+        sp, N, Msp, P_c, T = self._spectral, self.N, self.Ms_pad, len(props), 128
         Zgd, Zmd, Zdd = (self._workspace2d(nm, T, N) for nm in ("Zg_d", "Zm_d", "Zd_d"))
         Vd = [self._workspace2d("Vd_%d" % jj, T, N) for jj in range(P_c)]
         tmp = [self._workspace2d("Vt_%d" % jj, T, N) for jj in range(P_c)]
-        gens_d = [sp.eigenvalues(self._cov_table(hip.kernel_id(name, 2 != j), lengths[j], lengths[2], W[2][j], amp)) for j in props]
+        gens_g, gens_m = [step.gens[(0, j)] for j in props], [step.gens[(1, j)] for j in props]
+        gens_d = [sp.eigenvalues(step.prior.table(self, 2, j)) for j in props]
         acc = torch.zeros((P_c, N), dtype=F64, device=self.device)
         for c0 in range(d0, d0 + nd, T):
             n = min(T, d0 + nd - c0)

@@ -87,6 +87,7 @@ def main():
     import geobo_amd.engine as E
     from geobo_amd import hip
     from geobo_amd.sharding import EmulatedGroup
+    from geobo_amd.step import Prior
     n, G = a.size, a.world
     s = settings(n)
     os.environ.setdefault("GEOBO_ROWS", "1")            # (sizes below the planner's threshold, e.g. --size 32 in the test tier)
@@ -94,7 +95,6 @@ def main():
     eng = E.PosteriorEngine(s, rank=a.rank, world=G, group=EmulatedGroup(a.rank, G), assembly="f32", operators="streamed")
     assert eng.route.family == "rows", eng.route
     props, lengths, W, name = (0, 1, 2), [200.0, 202.0, 204.0], E.weight_matrix(s.gp_coeff), "matern32"
-    eng._W = W
     N, Ms, Msp = eng.N, eng.Ms, eng.Ms_pad
     rho, chi, loc, sel = survey(eng, s, n, a.drill)
     sel_t = torch.as_tensor(sel, device="cuda") if sel.size else None
@@ -122,7 +122,7 @@ def main():
         A_g, A_m = stage("operators (plans, Q, slabs)", lambda: (eng.operator("grav", loc, B=s.magneticField * 0.), eng.operator("magn", loc, B=s.magneticField)))
         eng._spectral_product()
         assert eng._rows_ok(A_g, A_m)
-        eng._rowpath = True
+        step = eng._new_step(Prior(name, lengths, W, 1.0), props, sel_t, s.gp_err, rowpath=True)    # (the row form, as _assemble_AK decides it)
         z = lambda v: (v - v.mean()) / v.std()
         vd = lambda v: hip.to_dev(np.asarray(v).reshape(-1, 1))
         grav = apply_rows(eng, A_g, vd(rho))[:, 0].cpu().numpy().astype(np.float32).astype(np.float64)
@@ -138,14 +138,14 @@ def main():
                 continue
             eng.rank = r
             key = "A K -> AkA row blocks (this rank)" if r == a.rank else "AkA row blocks of the %d peers" % (G - 1)
-            lo, dr = stage(key, lambda: eng._rows_aka_local(props, sel_t, lengths, W, name, 1.0), quiet=r != a.rank)
+            lo, dr = stage(key, lambda: eng._rows_aka_local(step), quiet=r != a.rank)
             blocks[r] = lo.clone() if G > 1 else lo
             drill = dr
         eng.rank = a.rank
         AkA = eng._workspace("AkA", (M_pad, M_pad))
         AkA.zero_()
         eng._rows_aka_place(AkA, blocks, drill, sel_t)
-        eng._finish_AkA(AkA, M_pad, sel_t, lengths, name, 1.0, s.gp_err)
+        eng._finish_AkA(step, AkA)
         peers = blocks
         del blocks
         AkA_low = None
@@ -169,7 +169,7 @@ def main():
         st = stats.cpu().numpy()
         logl = -0.5 * (st[0] + st[1] + N * np.log(2 * np.pi))
         # ---- posterior: this rank's share (timed); --sequential: every rank's ----------------------------------------------------------
-        mu_t, var_t = stage("posterior (this rank's rows)", lambda: eng._posterior_rows(Linv, u, sel_t, lengths, W, name, 1.0, props, M_pad))
+        mu_t, var_t = stage("posterior (this rank's rows)", lambda: eng._posterior_rows(step, Linv, u))
         mu = mu_t.cpu().numpy().reshape(3, N)
         part = (1.0 - var_t).cpu().numpy().reshape(3, N)          # the rank's partial sums of squares (the all-reduce is the identity here)
         total_ss = part.copy()
@@ -177,7 +177,7 @@ def main():
             for r in range(G):
                 if r != a.rank:
                     eng.rank = r
-                    _, v_r = stage("posterior shares of the %d peers" % (G - 1), lambda: eng._posterior_rows(Linv, u, sel_t, lengths, W, name, 1.0, props, M_pad),
+                    _, v_r = stage("posterior shares of the %d peers" % (G - 1), lambda: eng._posterior_rows(step, Linv, u),
                                    quiet=True)
                     total_ss += (1.0 - v_r).cpu().numpy().reshape(3, N)
             eng.rank = a.rank
@@ -204,7 +204,7 @@ def main():
         one = torch.zeros((sp.R, eng.N_pad), dtype=torch.float64, device="cuda")
         outs = [torch.empty((sp.R, N), dtype=torch.float64, device="cuda") for _ in props]
         for s_, op in ((0, A_g), (1, A_m)):
-            gens = [eng._gens[(s_, j)] for j in props]
+            gens = [step.gens[(s_, j)] for j in props]
             for k, r in enumerate(sens):
                 w = {j: O.ak_row_fft(Gd, Ao[s_][k], name, ln, Wn, s_, j) for j in props}
                 one[0, :N] = torch.as_tensor(Ao[s_][k], device="cuda")

@@ -28,6 +28,12 @@ def _inv(s, **kw):
     return inv
 
 
+def _step(eng, lengths, W, props, sel_t, noise, **kw):
+    """The Step posterior() builds for a Matern-3/2 prior of amplitude 1 (the engine's assembly stages take it)."""
+    from geobo_amd.step import Prior
+    return eng._new_step(Prior("matern32", lengths, W, 1.0), props, sel_t, noise, **kw)
+
+
 def elementwise_rel(c, r, floor=1e-3):
     """max |c - r| / |r| over the voxels where |r| > floor * max|r| (element-wise relative error is only meaningful away from
     the zero crossings of the posterior mean; the normwise figure covers the rest)."""
@@ -440,12 +446,12 @@ def test_symmetric_gram_plan_matches_the_block_column_form(dims, md):
     sel_t = torch.as_tensor(sel, device="cuda") if md else None
     lengths = [float(v) for v in E.create_cov_lengths(np.array([200.0, 202.0, 204.0]))]
     W = E.weight_matrix(s.gp_coeff)
-    eng._W = W
     out = {}
     for sym in (False, True):
         assert (not sym) or eng._sym_ok(A_g, A_m)
-        AK, M_pad = eng._assemble_AK(A_g, A_m, sel_t, lengths, W, "matern32", 1.0, (0, 1), sym=sym)
-        out[sym] = torch.tril(eng._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, lengths, "matern32", 1.0, s.gp_err, (0, 1))).clone()
+        step = _step(eng, lengths, W, (0, 1), sel_t, s.gp_err, sym=sym)
+        AK = eng._assemble_AK(step, A_g, A_m)
+        out[sym] = torch.tril(eng._assemble_AkA(step, AK, A_g, A_m)).clone()
     d = (out[True] - out[False]).abs().max().item() / out[False].abs().max().item()
     print(dims, "symmetric plan vs block columns: %.2e" % d)
     assert d <= 1e-13
@@ -745,7 +751,8 @@ def test_column_shards_reproduce_the_unsharded_posterior():
         eng.c0, eng.c1 = shard_columns(eng.N_pad, world, r)      # this engine plays rank r of a 3-way split
         eng.nc = eng.c1 - eng.c0
         A_g, A_m = eng.operator("grav", f["sensor_locations"]), eng.operator("magn", f["sensor_locations"])
-        AK, M_pad = eng._assemble_AK(A_g, A_m, sel_t, lengths, W, "matern32", 1.0, (0, 1, 2))
+        step = _step(eng, lengths, W, (0, 1, 2), sel_t, s.gp_err)
+        AK, M_pad = eng._assemble_AK(step, A_g, A_m), step.M_pad
         AkA = torch.zeros((M_pad, M_pad), dtype=torch.float64, device="cuda")
         for s_, A in ((0, A_g), (1, A_m)):
             hip.gemm_nt(AK[:, s_ * eng.nc:(s_ + 1) * eng.nc], A[:, eng.c0:eng.c1], AkA[:, s_ * eng.Ms_pad:(s_ + 1) * eng.Ms_pad])
@@ -935,7 +942,7 @@ def _independent_checks_64(inv, s, G, Ag_o, Am_o, sens, lengths, W, what):
             r = sens[k]
             w = {j: O.ak_row_fft(G, A_o[k], "matern32", lengths, W, s_, j) for j in (0, 1, 2)}
             for jj, j in enumerate((0, 1)):                                  # rows of A K (the spectral product, P_c = 2)
-                if eng._ak_sym and (s_, j) == (1, 0):
+                if eng.last["step"].sym and (s_, j) == (1, 0):
                     continue     # not assembled: AkA's lower-left block is the transpose of (grav rows, magn columns) -- checked below
                 got = AK[off[s_] + r, jj * N:(jj + 1) * N].cpu().numpy()
                 e = np.abs(got - w[j]).max() / np.abs(w[j]).max()
@@ -950,10 +957,8 @@ def _independent_checks_64(inv, s, G, Ag_o, Am_o, sens, lengths, W, what):
             assert e <= 1e-11                                                # observed <= 8e-14
     # the factor itself: || tril(L) tril(L)^T - AkA || / || AkA || on the device (AkA re-assembled from the resident A K)
     Lc = Lt.clone()
-    M_pad = L.shape[0]
-    sel_t = torch.as_tensor(sel, device="cuda")
     A_g, A_m = inv._operators()
-    AkA2 = eng._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, [float(x) for x in lengths], "matern32", 1.0, s.gp_err, (0, 1))
+    AkA2 = eng._assemble_AkA(eng.last["step"], AK, A_g, A_m)
     AkA2 = torch.tril(AkA2)
     R = torch.tril(Lc @ Lc.t()) - AkA2
     e = (torch.linalg.matrix_norm(R) / torch.linalg.matrix_norm(AkA2)).item()
@@ -978,7 +983,7 @@ def test_spectral_y_slab_shards_match_dense(monkeypatch):
             eng = E.PosteriorEngine(s, rank=r, world=world, method=method)
             assert eng.use_spectral == (method == "spectral")
             A_g, A_m = eng.operator("grav", f["sensor_locations"]), eng.operator("magn", f["sensor_locations"])
-            out[method], _ = eng._assemble_AK(A_g, A_m, sel_t, lengths, W, "matern32", 1.0, (0, 1, 2))
+            out[method] = eng._assemble_AK(_step(eng, lengths, W, (0, 1, 2), sel_t, s.gp_err), A_g, A_m)
         d = (out["dense"] - out["spectral"]).abs().max().item()
         assert d <= 1e-12 * out["dense"].abs().max().item(), (r, d)
 
@@ -1062,14 +1067,15 @@ def test_row_sharded_exchange_matches_dense_columns():
             assert torch.equal(e._Arows[k][:, :e.N], Af[k][e.rank * rows_r:(e.rank + 1) * rows_r, :e.N])
         from geobo_amd.spectral import SpectralProduct
         e._spectral = SpectralProduct(e.nx, e.ny, e.nz, e.device)
-        sends.append([e._exchange_send(s_, func, lengths, W, "matern32", 1.0, props).clone() for s_, func in ((0, "grav"), (1, "magn"))])
+        step = _step(e, lengths, W, props, sel_t, s.gp_err)
+        sends.append([e._exchange_send(step, s_, func).clone() for s_, func in ((0, "grav"), (1, "magn"))])
     for r, e in enumerate(engs):
         M_pad = E.hip.pad_m(2 * e.Ms_pad + f["sel"].size)
         AK = torch.zeros((M_pad, len(props) * e.nc), dtype=torch.float64, device="cuda")
         for s_ in (0, 1):               # what the all-to-all of operator s_ delivers to rank r: block r of every source's buffer
             e._exchange_place(AK, torch.stack([sends[src][s_][r] for src in range(world)]), props, s_)
         d = E.PosteriorEngine(s, rank=r, world=world, method="dense")
-        ref, _ = d._assemble_AK(Af["grav"], Af["magn"], sel_t, lengths, W, "matern32", 1.0, props)
+        ref = d._assemble_AK(_step(d, lengths, W, props, sel_t, s.gp_err), Af["grav"], Af["magn"])
         rows = np.r_[0:e.Ms, e.Ms_pad:e.Ms_pad + e.Ms]
         diff = (AK[rows] - ref[rows]).abs().max().item()
         assert diff <= 1e-12 * ref.abs().max().item(), (r, diff)
@@ -1097,8 +1103,9 @@ def test_row_sharded_lattice_gram_matches_the_single_rank_AkA():
     props = (0, 1)
     ref_eng = E.PosteriorEngine(s)
     A_g, A_m = ref_eng.operator("grav", loc), ref_eng.operator("magn", loc)
-    AK, M_pad = ref_eng._assemble_AK(A_g, A_m, sel_t, lengths, W, "matern32", 1.0, props)
-    ref = torch.tril(ref_eng._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, lengths, "matern32", 1.0, s.gp_err, props)).clone()
+    step = _step(ref_eng, lengths, W, props, sel_t, s.gp_err)
+    AK, M_pad = ref_eng._assemble_AK(step, A_g, A_m), step.M_pad
+    ref = torch.tril(ref_eng._assemble_AkA(step, AK, A_g, A_m)).clone()
     del ref_eng, A_g, A_m, AK
     torch.cuda.empty_cache()
     world = 4
@@ -1110,7 +1117,7 @@ def test_row_sharded_lattice_gram_matches_the_single_rank_AkA():
         e._spectral_product()
         assert e._rows_ok(Ag_r, Am_r)
         # this rank's rows of A K -- (grav, 0), (grav, 1), (magn, 1) -- a chunk at a time, straight through the lattice Gram
-        lo, dr = e._rows_aka_local(props, sel_t, lengths, W, "matern32", 1.0)
+        lo, dr = e._rows_aka_local(_step(e, lengths, W, props, sel_t, s.gp_err))
         blocks.append(lo.clone())
         drill = dr.clone()
         del e, lo, dr
@@ -1125,7 +1132,7 @@ def test_row_sharded_lattice_gram_matches_the_single_rank_AkA():
         AkA[Msp + r0:Msp + r0 + rows_r, Msp:off_d] = blocks[src][:, off_d:]
     AkA[Msp:off_d, :Msp] = AkA[:Msp, Msp:off_d].t()
     AkA[off_d:off_d + Md, :off_d] = drill[:Md]
-    got = torch.tril(eng._finish_AkA(AkA, M_pad, sel_t, lengths, "matern32", 1.0, s.gp_err))
+    got = torch.tril(eng._finish_AkA(_step(eng, lengths, W, props, sel_t, s.gp_err), AkA))
     d = (got - ref).abs().max().item()
     assert d <= 1e-12 * ref.abs().max().item(), d
 
@@ -1193,10 +1200,10 @@ def test_lattice_gram_matches_the_gemm(ny, monkeypatch):
         eng = E.PosteriorEngine(s)
         A_g, A_m = eng.operator("grav", loc), eng.operator("magn", loc)
         assert (eng._lam.get("grav") is not None) == (flag == "1")
-        AK, M_pad = eng._assemble_AK(A_g, A_m, sel_t, lengths, W, "matern32", 1.0, (0, 1))
-        AkA = eng._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, lengths, "matern32", 1.0, s.gp_err, (0, 1))
+        step = _step(eng, lengths, W, (0, 1), sel_t, s.gp_err)
+        AkA = eng._assemble_AkA(step, eng._assemble_AK(step, A_g, A_m), A_g, A_m)
         out[flag] = torch.tril(AkA).clone()
-        del eng, A_g, A_m, AK, AkA
+        del eng, A_g, A_m, step, AkA
         torch.cuda.empty_cache()
     d = (out["0"] - out["1"]).abs().max().item()
     assert d <= 1e-12 * out["0"].abs().max().item(), d
@@ -1261,10 +1268,10 @@ def test_lattice_gram_y_slab_shards_add_up(world, monkeypatch):
             eng = E.PosteriorEngine(s, rank=r, world=world)
             A_g, A_m = eng.operator("grav", loc), eng.operator("magn", loc)
             assert (eng._lam.get("grav") is not None) == (flag == "1")
-            AK, M_pad = eng._assemble_AK(A_g, A_m, sel_t, lengths, W, "matern32", 1.0, (0, 1))
-            AkA = torch.tril(eng._assemble_AkA(AK, M_pad, A_g, A_m, sel_t, lengths, "matern32", 1.0, s.gp_err, (0, 1)))
+            step = _step(eng, lengths, W, (0, 1), sel_t, s.gp_err)
+            AkA = torch.tril(eng._assemble_AkA(step, eng._assemble_AK(step, A_g, A_m), A_g, A_m))
             acc = AkA.clone() if acc is None else acc + AkA
-            del eng, A_g, A_m, AK, AkA
+            del eng, A_g, A_m, step, AkA
             torch.cuda.empty_cache()
         total[flag] = acc
     d = (total["0"] - total["1"]).abs().max().item()

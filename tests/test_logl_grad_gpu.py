@@ -272,8 +272,51 @@ def test_neg_logl_and_grad_illconditioned_matern_spectral():
 
 
 # ---- 6. non-interference ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,kern,shape", [("tiny_exp", "exp", TINY), ("cube16_exp", "exp", (16, 16, 16))])
-def test_gradient_leaves_later_steps_unchanged(name, kern, shape):
+def _lattice_non_interference(family, kern, shape, monkeypatch):
+    """A lattice survey on the smallest grids that reach the one-rank families of the structured step: "single" at 64 x 48 x 64 (the
+    smallest grid with the fused lattice Gram, which the symmetric plan of A K needs; 64 x 16 x 64 is planned "single" too, but its
+    AkA is a GEMM and the step runs as "columns") and "rows" at 64 x 16 x 64 (forced: below the row form's threshold).  A gradient at
+    other hyper-parameters (one zero weight: the unit-weight Gram as well) and one at the step's own with three directions (one with
+    a zero component) sit between two predict3 calls, which must agree bit for bit; so must the set statistics of the factor of the
+    step's own hyper-parameters before and after the derivative Grams were assembled beside it."""
+    import os
+    import bench
+    from geobo_amd.plan import plan_route
+    if family == "rows":
+        monkeypatch.setenv("GEOBO_ROWS", "1")
+    assert plan_route(*shape, world=1, rank=0, assembly="f64", operators="auto", method="auto", env=os.environ).family == family
+    inv = _inv(settings_for(*shape, kernelfunc=kern))                # (operators="auto": Inversion's default)
+    grav, mag, loc, drill0 = bench.synthetic_inputs(inv, 20)
+    inv.gp_length = np.array([200.0, 202.0, 204.0])
+    inv.cubing(grav, mag, drill0[drill0 != 0], loc, drill0)
+    eng, (nx, ny, nz) = inv.engine, shape
+    lengths = [float(v) for v in inv.gp_length]
+    sets = np.array([(iy * nx + ix) * nz for iy, ix in ((0, 0), (3, 17), (8, 63), (15, 40), (7, 7))])[:, None] + np.arange(16)[None, :]
+    stats = lambda: [t.cpu().numpy() for t in eng.set_statistics(sets, kern, lengths, inv.coeffm, inv.gp_amp, inv.gp_sigma)]
+    mu0, cov0, logl0 = inv.predict3(calclogl=True)
+    assert eng.step_route == family
+    st0 = stats()
+    assert (st0[3] == 0).all() and np.isfinite(st0[0]).all()
+    val, grad = inv.neg_logl_and_grad(1.2, [220.0, 224.0, 228.0], [0.0, 0.4, 0.3])          # (Matern-3/2: three distinct lengths)
+    assert np.isfinite(val) and np.isfinite(grad).all() and eng.step_route == family
+    A_g, A_m = eng.last["ops"]
+    ng = grav.size
+    r = eng.logl_grad(A_g, A_m, eng.last["sel"], inv.Fs3[:ng], inv.Fs3[ng:2 * ng], inv.Fs3[2 * ng:], lengths, inv.coeffm, kern, inv.gp_sigma,
+                      inv.gp_amp, [[100.0, 102.0, 100.0], [50.0, -25.0, 10.0], [0.0, 30.0, -60.0]])
+    assert np.isfinite(r["d_dir"]).all() and r["d_dir"].shape == (3,)
+    st1 = stats()
+    for a, b in zip(st0, st1):
+        assert np.array_equal(a, b)
+    mu1, cov1, logl1 = inv.predict3(calclogl=True)
+    assert np.array_equal(mu0, mu1, equal_nan=True) and np.array_equal(np.diag(cov0), np.diag(cov1), equal_nan=True)
+    assert logl0 == logl1
+
+
+@pytest.mark.parametrize("name,kern,shape", [("tiny_exp", "exp", TINY), ("cube16_exp", "exp", (16, 16, 16)),
+                                             ("lattice_single", "matern32", (64, 48, 64)), ("lattice_rows", "matern32", (64, 16, 64))])
+def test_gradient_leaves_later_steps_unchanged(name, kern, shape, monkeypatch):
+    if name.startswith("lattice_"):
+        return _lattice_non_interference(name.split("_")[1], kern, shape, monkeypatch)
     f, s, inv = _loaded(name, kern, shape)
     mu0, cov0, logl0 = inv.predict3(calclogl=True)
     inv.calc_logl_grad([1.2, 2.2, 0.0, 0.4, 0.3])
