@@ -332,7 +332,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                     # "auto" and the stencil is not even (no lattice Gram): AkA is an N-deep GEMM against the operator -- resident
                     self._auto_denied.add(dkey)
                     return self.operator(func, sensor_locations, B=B, axes=axes, full=full)
-                if self.use_spectral and self._spectral_product().lattice_feed and not self.f32:
+                if self.use_spectral and self._spectral_product().forms.lattice_feed and not self.f32:
                     self._timed("a_sens_" + func, 0.0, lambda: A.keep_stencil(func))
             self._lam[func] = None if lam is None else (A, lam)
             if rows_mode:
@@ -423,13 +423,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         from .lattice_gram import LatticeGram
         if not LatticeGram.supported(self.nx, self.ny, self.nz) or self.Ms_pad != self.Ms:
             return False
-        return self._spectral_product().lattice_feed
+        return self._spectral_product().forms.lattice_feed
 
     def _spectral_product(self):
         """The grid's SpectralProduct, its per-kernel timer following the engine's kernel_events switch."""
         from .spectral import SpectralProduct
         if self._spectral is None:
-            self._spectral = SpectralProduct(self.nx, self.ny, self.nz, self.device, opts=self.route.opts())
+            self._spectral = SpectralProduct(self.nx, self.ny, self.nz, self.device, forms=self.route.forms)
         self._spectral.kernel_timer = None if self.kernel_events is None else (
             lambda name, by, fn, valu=0.0, flop=0.0: self._timed(name, flop, fn, alg=by, valu=valu))
         return self._spectral

@@ -19,7 +19,8 @@ KERNEL_IDS = {"d2": 0, "exp": 1, "exp_x": 2, "matern32": 3, "matern32_x": 4, "sp
               "sparse_dl": 13, "sparse_x_dl1": 14, "sparse_x_dl2": 15}
 FUNC_IDS = {"grav": 0, "magn": 1}
 # kernel-instance tables and padding units: ONE definition (plan.py, which decides routes from them on the CPU); re-exported here
-from .plan import PAD_M, PAD_N, SPECTRAL_AXIS_N, SPECTRAL_Y_NY, TOEPLITZ_NY, XZ2D_FOLD_N, XZ2D_SHAPES  # noqa: E402,F401
+from .plan import (PAD_M, PAD_N, SPECTRAL_AXIS_N, SPECTRAL_Y3T_NY, SPECTRAL_Y_NY, TOEPLITZ_ADD_NY, TOEPLITZ_NY, TOEPLITZ_Y2T_NY,  # noqa: E402,F401
+                   XZ2D_FOLD_N, XZ2D_SHAPES, YMUL_SHAPES)
 
 
 def kernel_id(name, cross, deriv=None):
@@ -527,7 +528,7 @@ def xz2d_fold_lattice(n, rows, ppr, Q, row_off, q_plane, edge, edge_row, Fx, Fz,
                                            _p(_chk(out, "out")), int(out_row), int(out_plane), _stream()), "geobo_xz2d_fold_lattice")
 
 
-YMUL_SHAPES = ((128, 64),)      # (m, k) geobo_ymul is instantiated for
+# YMUL_SHAPES (plan.py): (m, k) geobo_ymul is instantiated for
 
 
 def ymul(m, k, C, rows, G, src, in_row, out, out_row, fold=False):
@@ -564,7 +565,7 @@ def a_sens_lattice_stencil(ws, nx, ny, nz):
 # TOEPLITZ_NY (plan.py): y extents geobo_toeplitz_y / _y3 are instantiated for
 
 
-TOEPLITZ_ADD_NY = (80, 96, 112, 128)      # y extents of the accumulating form (geobo_toeplitz_y3_add)
+# TOEPLITZ_ADD_NY (plan.py): y extents of the accumulating form (geobo_toeplitz_y3_add)
 
 
 def toeplitz_y(ny, C, R, src, tabs, outs, y0=0, y1=None, plane=None, accumulate=False):
@@ -582,7 +583,7 @@ def toeplitz_y(ny, C, R, src, tabs, outs, y0=0, y1=None, plane=None, accumulate=
     _lib.check(fn(int(ny), int(C), int(C if plane is None else plane), int(R), n, _p(_chk(src, "src")), tp, op, int(y0), int(y1), _stream()), name)
 
 
-TOEPLITZ_Y2T_NY = (32, 48, 64)      # y extents of the two-term kernel
+# TOEPLITZ_Y2T_NY (plan.py): y extents of the two-term kernel
 
 
 def toeplitz_y2t(ny, C, R, src_g, src_m, tabs_g, tabs_m, outs, plane=None):
@@ -638,7 +639,7 @@ def spectral_y(ny, C, R, src, tabs, outs, y0=0, y1=None, plane=None, accumulate=
                                      1 if accumulate else 0, _p(spectral_y_basis(ny, src.device)), _stream()), "geobo_spectral_y3")
 
 
-SPECTRAL_Y3T_NY = (80, 96, 112, 128)      # y extents of the two-term long-axis form (geobo_spectral_y3t)
+# SPECTRAL_Y3T_NY (plan.py): y extents of the two-term long-axis form (geobo_spectral_y3t)
 
 
 def spectral_y3t(ny, C, R, src_g, src_m, tabs_g, tabs_m, outs, plane=None):

@@ -49,10 +49,8 @@ class LatticeGram:
         # rows per batch: 256 where the fused kernels run (1 GB of y-step output at 64^3); the shape-independent x step keeps
         # D = Gx X for a whole batch (Py Px nz doubles per row: 67 MB at 128^3), ~2 GB per buffer
         per_row = self.Py * self.Px * self.nz * 8
-        dflt = 256 if self.fast(self.nx, self.ny, self.nz) else max(8, min(256, (2 << 30) // per_row))
-        self.R = dflt
-        # rows per batch of the transposed application (W = Lambda * lhat is Px nz Py doubles per row: 8.4 MB at 64^3, 67 MB at 128^3)
-        self.Rz = self.R if self.fast(self.nx, self.ny, self.nz) else max(8, min(256, (2 << 30) // per_row))
+        # ... and of the transposed application (W = Lambda * lhat is Px nz Py doubles per row: 8.4 MB at 64^3, 67 MB at 128^3)
+        self.R = self.Rz = 256 if self.fast(self.nx, self.ny, self.nz) else max(8, min(256, (2 << 30) // per_row))
         self.J = (self.ny + 63) // 64 * 64                          # jy slots of the boundary-slab spectra (whole 64-row halves of a GEMM tile)
         self._lam_oz = {}
 
@@ -151,25 +149,32 @@ class LatticeGram:
         """LambdaW[kx][iz][ky] from the Gram's eigen-data lam = Lambda^T[ky][z][kx] / (Py Px)."""
         return lam.view(self.Py, self.nz, self.Px).permute(2, 1, 0).contiguous().view(-1)
 
-    def _lhat(self, Lrows, r0, Rb, lh):
-        """lh[r] (Py x Px) = Gy l_r Gx^T for the sensor images l_r = Lrows[r0 + r] (ny x nx): the radix-2 / fused two-axis kernels where
-        they are instantiated, two batched GEMM passes otherwise."""
+    def _plane_yx(self, inverse, R, src, ld_src, dst, ld_dst):
+        """R square (y, x) planes through both axes, rows ld_src / ld_dst doubles apart: forward, sensor images l (ny x nx) -> Gy l Gx^T
+        (Py x Px); inverse, S (Py x Px) -> Gy^T S Gx (ny x nx).  The radix-2 / fused two-axis kernels where they are instantiated ("x" of
+        geobo_xz2d is this grid's y axis, its "z" this grid's x axis), two batched GEMM passes otherwise (forms.plane_yx)."""
         nx, ny, Px, Py, sp = self.nx, self.ny, self.Px, self.Py, self.sp
-        if sp.fold and ny == nx and "y" in sp.F:
-            hip.xz2d_fold(False, ny, Rb, 1, Lrows[r0:], Lrows.stride(0), ny * nx, sp.F["y"], sp.F["x"], lh, Py * Px, Py * Px)
-        elif (ny, nx) in hip.XZ2D_SHAPES:
-            hip.xz2d(False, ny, nx, Rb, 1, Lrows[r0:], Lrows.stride(0), ny * nx, sp.G["y"], sp.G["x"], lh, Py * Px, Py * Px)
+        form, fold = sp.forms.plane_yx, sp.forms.fold
+        p_src, p_dst = (Py * Px, ny * nx) if inverse else (ny * nx, Py * Px)
+        if form == "fold":
+            hip.xz2d_fold(inverse, ny, R, 1, src, ld_src, p_src, sp.F["y"], sp.F["x"], dst, ld_dst, p_dst)
+        elif form == "fused":
+            M = sp.GT if inverse else sp.G
+            hip.xz2d(inverse, ny, nx, R, 1, src, ld_src, p_src, M["y"], M["x"], dst, ld_dst, p_dst)
+        elif inverse:
+            t1 = sp.buf("LG_Bt", R * ny * Px + hip.pad_n(ny) * Px)             # [row][iy][kx]
+            hip.axis_pass(fold, True, True, hip.pad_n(ny), hip.pad_n(Px), Py, sp.GT["y"], Py, 0, src, Px, ld_src, t1, Px, ny * Px, ny, Px, R)
+            hip.gemm_batched(True, hip.pad_n(ny), hip.pad_n(nx), Px, t1, Px, ny * Px, sp.G["x"], nx, 0, dst, nx, ld_dst, ny, nx, R)
         else:
-            src = Lrows[r0:]
             nyp = hip.pad_n(ny)
-            end = src.storage_offset() + (Rb - 1) * src.stride(0) + nyp * nx
+            end = src.storage_offset() + (R - 1) * ld_src + nyp * nx
             if end > src.untyped_storage().nbytes() // 8:                             # compute rows of the first pass overhang the image
-                Lc = sp.buf("LG_LX", Rb * ny * nx + nyp * nx)[:Rb * ny * nx].view(Rb, ny * nx)
-                Lc.copy_(src[:Rb, :ny * nx])
-                src = Lc
-            t1 = sp.buf("LG_Lt", Rb * ny * Px + nyp * Px)                             # [row][jy][kx]
-            hip.axis_pass(sp.fold, False, False, nyp, hip.pad_n(Px), nx, src, nx, src.stride(0), sp.G["x"], nx, 0, t1, Px, ny * Px, ny, Px, Rb)
-            hip.axis_pass(sp.fold, True, False, hip.pad_n(Py), hip.pad_n(Px), ny, sp.G["y"], ny, 0, t1, Px, ny * Px, lh, Px, Py * Px, Py, Px, Rb)
+                Lc = sp.buf("LG_LX", R * ny * nx + nyp * nx)[:R * ny * nx].view(R, ny * nx)
+                Lc.copy_(src[:R, :ny * nx])
+                src, ld_src = Lc, ny * nx
+            t1 = sp.buf("LG_Lt", R * ny * Px + nyp * Px)                             # [row][jy][kx]
+            hip.axis_pass(fold, False, False, nyp, hip.pad_n(Px), nx, src, nx, ld_src, sp.G["x"], nx, 0, t1, Px, ny * Px, ny, Px, R)
+            hip.axis_pass(fold, True, False, hip.pad_n(Py), hip.pad_n(Px), ny, sp.G["y"], ny, 0, t1, Px, ny * Px, dst, Px, ld_dst, Py, Px, R)
 
     def apply_transpose(self, Lrows, nrows, lamW, out):
         """out[r, :ny*nx*nz] = interior-slab part of  sum_c Lrows[r, c] A[c, :]  (boundary slabs zero), r < nrows.
@@ -185,23 +190,23 @@ class LatticeGram:
         for r0 in range(0, nrows, R):
             Rb = min(R, nrows - r0)
             lh = sp.buf("LG_Lh", R * Py * Px)
-            self._lhat(Lrows, r0, Rb, lh)
+            self._plane_yx(False, Rb, Lrows[r0:], Lrows.stride(0), lh, Py * Px)
             W = sp.buf("LG_W", R * Px * nz * Py)
             hip.lattice_wbuild(Rb, Py, Px, nz, lamW, lh, W)
             U = sp.buf("LG_U", R * nx * nz * Py)
-            if sp.x_mfma and (nz * Py) % 16 == 0 and 2 * nx * nz * Py * 8 < (1 << 31):
+            if sp.forms.x_axis4 and (nz * Py) % 16 == 0 and 2 * nx * nz * Py * 8 < (1 << 31):
                 # x synthesis as a radix-4 axis pass (geobo_spectral_axis): nz Py contiguous modes per plane, Px -> nx planes per row
                 hip.spectral_axis(True, nx, nz * Py, nz * Py, nz * Py, Px * nz * Py, nx * nz * Py, Rb, W, U)
             else:
-                hip.axis_pass(sp.fold, True, True, hip.pad_n(nx), nz * Py, Px, sp.GT["x"], Px, 0, W, nz * Py, Px * nz * Py, U, nz * Py, nx * nz * Py, nx, nz * Py, Rb)
-            hip.axis_pass(sp.fold and 2, False, 2, hip.pad_n(ny), nx * nz, Py, self._GyT0, Py, 0, U, Py, nx * nz * Py, out[r0:], nx * nz, out.stride(0), ny, nx * nz, Rb)
+                hip.axis_pass(sp.forms.fold, True, True, hip.pad_n(nx), nz * Py, Px, sp.GT["x"], Px, 0, W, nz * Py, Px * nz * Py, U, nz * Py, nx * nz * Py, nx, nz * Py, Rb)
+            hip.axis_pass(sp.forms.fold and 2, False, 2, hip.pad_n(ny), nx * nz, Py, self._GyT0, Py, 0, U, Py, nx * nz * Py, out[r0:], nx * nz, out.stride(0), ny, nx * nz, Rb)
 
     def transpose_tables3(self, lam):
         """Lambda3[iz][ky][kx] (spectral planes per z channel) from the Gram's eigen-data lam = Lambda^T[ky][z][kx] / (Py Px)."""
         return lam.view(self.Py, self.nz, self.Px).permute(1, 0, 2).contiguous().view(-1)
 
     def zx_supported(self):
-        return self.nx == self.ny == self.nz == 64 and self.sp.fold and "y" in self.sp.F and self.sp.opts["z_fused"]
+        return self.sp.forms.zx
 
     def apply_transpose_zx(self, Lrows, nrows, lam3, out):
         """The same product as apply_transpose with steps 2-4 as ONE fused inverse two-axis transform per (row, z channel) plane
@@ -216,8 +221,8 @@ class LatticeGram:
         for r0 in range(0, nrows, R):
             Rb = min(R, nrows - r0)
             lh = sp.buf("LG_Lh", R * Py * Px)
-            hip.xz2d_fold(False, ny, Rb, 1, Lrows[r0:], Lrows.stride(0), ny * nx, sp.F["y"], sp.F["x"], lh, Py * Px, Py * Px)
-            if self.sp.opts["z_mul"]:
+            self._plane_yx(False, Rb, Lrows[r0:], Lrows.stride(0), lh, Py * Px)
+            if sp.forms.z_mul:
                 # W[r][iz] = Lambda3[iz] * lhat_r is formed inside the inverse kernel, chunk by chunk, from the two cache-resident factors
                 hip.xz2d_fold_inv_mul(ny, Rb, nz, lam3, Py * Px, lh, Py * Px, sp.F["y"], sp.F["x"], out[r0:], out.stride(0), nx, nz * nx)
                 continue
@@ -313,11 +318,10 @@ class LatticeGram:
     def flops(self, rows, Ly=None):
         nx, ny, nz, Px, Py = self.nx, self.ny, self.nz, self.Px, self.Py
         Ly = ny if Ly is None else Ly
-        f = self.sp.fold and nx == nz == 64
-        h = 0.25 if f else 1.0            # radix-4 x step: a quarter of the MFMAs of the plain product
-        hb = 0.25 if f else 1.0           # back-transform on the radix-4 inverse kernel: a quarter
+        f = self.sp.forms.gram_x == "fold"
+        h = hb = 0.25 if f else 1.0       # radix-4 x step and back-transform on the radix-4 inverse kernel: a quarter of the MFMAs of the plain product
         zsum = 0.0 if self.fast(nx, ny, nz) else 2.0 * Py * Px * nz  # (the stand-alone scaling + channel sum of the batched-GEMM form, fp64 VALU)
-        hy = 0.5 if (f and (Py, Ly) in hip.YMUL_SHAPES) else 1.0     # y step on geobo_ymul_fold: radix 2
+        hy = 0.5 if (f and Ly in self.sp.forms.ymul_slabs) else 1.0     # y step on geobo_ymul_fold: radix 2
         return rows * (2.0 * (hy * hip.pad_n(Py) * nx * nz * Ly + h * Py * Px * nx * nz + hb * (ny * Py * Px + ny * nx * Px)) + zsum)
 
     def gram_rows(self, X, nrows, lam, out, y0=0, y1=None):
@@ -328,47 +332,38 @@ class LatticeGram:
         y1 = ny if y1 is None else y1
         Ly = y1 - y0
         assert Ly % 16 == 0
-        sp = self.sp
+        sp, f = self.sp, self.sp.forms
         plane = nx * nz
         assert X.stride(1) == 1 and out.stride(1) == 1 and X.stride(0) % 2 == 0 and out.stride(0) % 2 == 0
         gy = self.Gy0[:, y0:]                        # columns of this slab (row stride ny; rows behind are padding / slack)
         for r0 in range(0, nrows, self.R):
             R = min(self.R, nrows - r0)
             y1b = sp.buf("LG_Y1", R * Py * plane)
-            if (Py, Ly) in hip.YMUL_SHAPES and plane % 64 == 0:
+            if Ly in f.ymul_slabs and plane % 64 == 0:
                 # G_y in registers, rows streamed once; radix 2 where the slab starts on an even y (Gy0 keeps the pair structure: its
                 # zeroed columns are zero in both rows of a pair)
-                hip.ymul(Py, Ly, plane, R, gy, X[r0:], X.stride(0), y1b, Py * plane, fold=sp.fold and y0 % 2 == 0)
-            elif sp.axis_mfma(ny) and y0 == 0 and Ly == ny and plane % 16 == 0 and 2 * ny * plane * 8 < (1 << 31) and X.stride(0) >= ny * plane:
+                hip.ymul(Py, Ly, plane, R, gy, X[r0:], X.stride(0), y1b, Py * plane, fold=f.fold and y0 % 2 == 0)
+            elif f.gram_y_axis4 and y0 == 0 and Ly == ny and plane % 16 == 0 and 2 * ny * plane * 8 < (1 << 31) and X.stride(0) >= ny * plane:
                 # the whole y axis: radix-4 axis pass, the two boundary slabs masked inside the kernel (what Gy0's zeroed columns do)
                 hip.spectral_axis(False, ny, plane, plane, plane, X.stride(0), Py * plane, R, X[r0:], y1b, mask_ends=True)
             else:
                 # (radix-2 when the slab starts on an even y: the parity of the local input index is the basis row pair's)
-                hip.axis_pass(sp.fold and y0 % 2 == 0, True, False, hip.pad_n(Py), hip.pad_n(plane), Ly, gy, ny, 0, X[r0:], plane, X.stride(0),
+                hip.axis_pass(f.fold and y0 % 2 == 0, True, False, hip.pad_n(Py), hip.pad_n(plane), Ly, gy, ny, 0, X[r0:], plane, X.stride(0),
                               y1b, plane, Py * plane, Py, plane, R)
             s = sp.buf("LG_S", R * Py * Px)
-            if sp.fold and nx == nz and "x" in sp.F:
+            if f.gram_x == "fold":
                 hip.xcorr_reduce_fold(nx, R, Py, y1b, Py * plane, plane, sp.F["x"], lam, s, Py * Px, Px)
-            elif (nx, nz) == (64, 64):
+            elif f.gram_x == "plain":
                 hip.xcorr_reduce(nx, nz, R, Py, y1b, Py * plane, plane, sp.G["x"], lam, s, Py * Px, Px)
+            elif f.gram_x == "fold_lamdot":
+                # any other extent: D[r, ky] = Gx X[r, ky] as a batch of small GEMMs, then the eigenvalue scaling and the channel sum -- in one
+                # launch: radix-2 analysis with the scaling and the channel sum as its epilogue, D never written
+                hip.gemm_fold_lamdot(Px, nz, nx, sp.G["x"], nx, y1b, nz, plane, self.lam_oz(lam), Py, s, R * Py)
             else:
-                # any other extent: D[r, ky] = Gx X[r, ky] as a batch of small GEMMs, then the eigenvalue scaling and the channel sum
-                if sp.fold and nz <= 128:
-                    # one launch: radix-2 analysis with the scaling and the channel sum as its epilogue, D never written
-                    hip.gemm_fold_lamdot(Px, nz, nx, sp.G["x"], nx, y1b, nz, plane, self.lam_oz(lam), Py, s, R * Py)
-                else:
-                    D = sp.buf("LG_D", R * Py * Px * nz)
-                    hip.axis_pass(sp.fold, True, False, hip.pad_n(Px), hip.pad_n(nz), nx, sp.G["x"], nx, 0, y1b, nz, plane, D, nz, Px * nz, Px, nz, R * Py)
-                    hip.lamdot_z(R * Py, Py, Px, nz, D, self.lam_oz(lam), s)
-            # "x" of geobo_xz2d is this grid's y axis, its "z" this grid's x axis: S_r (Py x Px) -> Gy^T S_r Gx (ny x nx)
-            if sp.fold and ny == nx and "y" in sp.F:
-                hip.xz2d_fold(True, ny, R, 1, s, Py * Px, Py * Px, sp.F["y"], sp.F["x"], out[r0:], out.stride(0), ny * nx)
-            elif (ny, nx) in hip.XZ2D_SHAPES:
-                hip.xz2d(True, ny, nx, R, 1, s, Py * Px, Py * Px, sp.GT["y"], sp.GT["x"], out[r0:], out.stride(0), ny * nx)
-            else:
-                t1 = sp.buf("LG_Bt", R * ny * Px + hip.pad_n(ny) * Px)             # [row][iy][kx]
-                hip.axis_pass(sp.fold, True, True, hip.pad_n(ny), hip.pad_n(Px), Py, sp.GT["y"], Py, 0, s, Px, Py * Px, t1, Px, ny * Px, ny, Px, R)
-                hip.gemm_batched(True, hip.pad_n(ny), hip.pad_n(nx), Px, t1, Px, ny * Px, sp.G["x"], nx, 0, out[r0:], nx, out.stride(0), ny, nx, R)
+                D = sp.buf("LG_D", R * Py * Px * nz)
+                hip.axis_pass(f.fold, True, False, hip.pad_n(Px), hip.pad_n(nz), nx, sp.G["x"], nx, 0, y1b, nz, plane, D, nz, Px * nz, Px, nz, R * Py)
+                hip.lamdot_z(R * Py, Py, Px, nz, D, self.lam_oz(lam), s)
+            self._plane_yx(True, R, s, Py * Px, out[r0:], out.stride(0))
 
     def lam_oz(self, lam):
         """The Gram's eigen-data as [ky][kx][z] (what geobo_lamdot_z reads) from eigen()'s [ky][z][kx]."""

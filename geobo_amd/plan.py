@@ -1,7 +1,7 @@
 """Route planning: every shape / rank-count / precision decision of an inversion step as ONE pure function.
 
 `plan_route` maps (grid extents, world size, assembly precision, operator mode, method, environment overrides) to a `Route`: which
-algorithm family the engine runs (engine.py reads nothing else to decide) and which kernels carry each stage.  No device, no torch:
+algorithm family the engine runs (engine.py reads nothing else to decide) and which kernels carry each stage (`stage_forms`).  No device, no torch:
 the whole table is tested on the CPU for every BASELINE.json configuration x world in {1, 2, 4, 8}
 (tests/test_host_logic_cpu.py::test_route_table).  The behaviour-changing GEOBO_* environment switches are overrides INTO this
 function; what a step then does is recorded as `engine.route` / `engine.step_route` and in the bench line.
@@ -25,6 +25,12 @@ XZ2D_FOLD_N = (64,)                               # radix-2 instances (hip.XZ2D_
 TOEPLITZ_NY = (16, 32, 48, 64, 80, 96, 112, 128)               # Toeplitz y-stage instances (hip.TOEPLITZ_NY)
 SPECTRAL_AXIS_N = (80, 96, 112, 128)              # radix-4 axis passes (hip.SPECTRAL_AXIS_N); extents on the half-integer basis only
 SPECTRAL_Y_NY = (32, 48, 64, 80, 96, 112, 128)    # in-kernel spectral y stage on the matrix pipe (hip.SPECTRAL_Y_NY); > 64: geobo_spectral_y3 only
+TOEPLITZ_Y2T_NY = (32, 48, 64)                    # two-term y stage in one pass (geobo_toeplitz_y2t / _y2s; hip.TOEPLITZ_Y2T_NY)
+TOEPLITZ_ADD_NY = (80, 96, 112, 128)              # accumulating y stage (geobo_toeplitz_y3_add; hip.TOEPLITZ_ADD_NY)
+SPECTRAL_Y3T_NY = (80, 96, 112, 128)              # two-term long-axis spectral y stage (geobo_spectral_y3t; hip.SPECTRAL_Y3T_NY)
+YMUL_SHAPES = ((128, 64),)                        # (m, k) geobo_ymul is instantiated for (hip.YMUL_SHAPES)
+INTEGER_BASIS_N = (32, 64)                        # extents whose fused kernels (xz2d_fold.hip: n = 64 and the four-plane form of 32 x 32 planes) build the
+                                                  # integer basis of spectral.base_modes() internally; every other extent: half_integer()
 ROWS_MIN_VOXELS = 1 << 18                         # batched-GEMM forms of the row algorithm pay from 64^3 voxels ...
 ROWS_MIN_PLANE = 96 * 96                          # ... and (x, z) planes that fill the 128 x 128 GEMM tiles
 ROWS_MIN_VOXELS_MID, ROWS_MIN_PLANE_MID = 3 << 17, 64 * 64   # ... or from 393 216 voxels with planes of 4096 modes: 80^3 3345 / 4733 ms (52 / 183 GB),
@@ -38,10 +44,11 @@ ROWS_MIN_VOXELS_FUSED = 1 << 17                   # with fused / four-plane (x, 
                                                   # below: 64x32x32 101 / 80, 48x32x64 89 / 69, 32x64x32 87 / 77, 64x16x64 35 / 33
 
 
-# Every behaviour switch of a step, in ONE table: option -> the environment override that turns it off ("0").  plan_route is the only
-# reader of the environment; the engine hands the resolved options on (Route.opts()) to the spectral product, the lattice Gram and the
-# transposed posterior, which used to read os.environ themselves (round-5 review, item 8).  All of them are A/B and fallback-coverage
-# switches: the default of every option is "on", and every "off" path is a complete, tested form of the same arithmetic.
+# Every behaviour switch of a step, in ONE table: option -> the environment override that turns it off ("0").  They are resolved ONCE
+# (switches(); a product built on its own resolves the process environment the same way) into the kernel forms of stage_forms(): the spectral
+# product, the lattice Gram and the transposed posterior decide nothing.  The environment is also read for plan_route's family overrides
+# (GEOBO_ROWS, GEOBO_POSTERIOR, GEOBO_SPECTRAL_EXCHANGE) and the row form's batch size (GEOBO_ROW_CHUNK, rowform.py: a test knob).  All are
+# A/B and fallback-coverage switches: the default of every option is "on", every "off" path a complete, tested form of the same arithmetic.
 SWITCHES = {"fused_xz": "GEOBO_SPECTRAL_FUSED_XZ",   # fused (x, z) transform kernels (else two batched passes)
             "fold": "GEOBO_XZ_FOLD",                 # radix-2 / radix-4 transform kernels (else the plain products)
             "quad": "GEOBO_XZ_QUAD",                 # 32 x 32 planes four at a time through the n = 64 radix-2 kernels (else stacked pairs)
@@ -59,6 +66,63 @@ def switches(env=None):
     """{option: bool} from an environment-like mapping (None: every option on)."""
     env = {} if env is None else env
     return {k: env.get(v, "1") != "0" for k, v in SWITCHES.items()}
+
+
+def half_integer(n):
+    """True where the axis runs on the HALF-INTEGER (skew-circulant) basis (round 6): a symmetric Toeplitz block of size n is also the
+    leading block of the skew-circulant of size P = 2n (first column k_0 .. k_{n-1}, *, -k_{n-1} .. -k_1), diagonalised by cos / sin of
+    the frequencies kappa = 1/2 .. n - 1/2 with eigenvalues sum_d w_d k(d) cos(2 pi kappa d / P).  No frequency is its own mirror or
+    quarter-period image, so all n frequencies fall into n/4 orbits {kappa, n - kappa, n/2 + kappa, n/2 - kappa} of ONE shape -- what
+    the radix-4 axis kernels of spectral_y.hip want.  Every consumer of G / G^T / E treats the spectral index as opaque (the eigen-data
+    go through the same matrices), and the pair structure row 2b+1 = (-1)^i row 2b of the radix-2 passes holds for every pair."""
+    return n not in INTEGER_BASIS_N
+
+
+@dataclass(frozen=True)
+class Forms:
+    """Which kernel form carries each stage of the spectral route on one grid (stage_forms): what SpectralProduct and LatticeGram run on."""
+    xz: str              # (x, z) transform of the covariance product: "fold" (radix-2 / radix-4 fused kernels) | "fused" (plain fused kernel) |
+                         # "quad" | "pair" (32 x 32 planes by fours on the radix-2 / by pairs on the (64, 32) fused kernel) | "gemm" (two passes).
+                         # Per call the eigen-matrices take the plain twin (fold -> fused, quad -> pair); odd slabs step down quad -> pair -> gemm
+    x_axis4: bool        # the x passes of "gemm" (and the x synthesis of the lattice rows) as radix-4 axis kernels (geobo_spectral_axis)
+    y: str               # "mfma" (in-kernel spectral product on the matrix pipe) | "toeplitz" (direct vector-pipe kernels) | "spectrum" (by passes)
+    y_two_term: str      # two-term rows: "y2t" (one pass for both terms) | "add" (the second term accumulates) | "separate" (two spectra, summed later)
+    y3t: bool            # ... "add" in one pass of the long-axis spectral kernel (geobo_spectral_y3t)
+    y2s: bool            # ... "y2t" with the shared cross block K_01 = K_10: three products instead of four
+    fold: bool           # the radix-2 switch as the batched passes see it (hip.axis_pass)
+    ss: str              # posterior sums of squares: "fused" (inside the inverse transform) | "stored" (a batch of V rows, then geobo_sumsq_accum)
+    lattice_feed: bool   # operator rows read from a lattice survey's stencil table by the radix-2 forward kernel
+    plane_yx: str        # the (ny, nx) two-axis transform of the lattice Gram / lattice rows: "fold" | "fused" | "gemm"
+    gram_x: str          # the Gram's x step: "fold" (geobo_xcorr_reduce_fold) | "plain" (geobo_xcorr_reduce) | "fold_lamdot" | "gemm"
+    gram_y_axis4: bool   # the Gram's y step over the whole axis as a radix-4 axis kernel
+    zx: bool             # rows of L^-1 A by one fused inverse transform per (row, z) plane, written as [iy][iz][ix]
+    z_mul: bool          # ... its input product formed inside the kernel
+    ymul_slabs: tuple    # slab heights whose Gram y step runs on geobo_ymul
+
+    def folded_axes(self):                # axes whose folded (radix-2) matrices some stage of this record reads
+        xz = self.xz == "fold" or self.lattice_feed or self.ss == "fused"
+        return tuple(a for a, used in (("x", xz or self.gram_x == "fold" or self.plane_yx == "fold"), ("y", self.plane_yx == "fold"), ("z", xz)) if used)
+
+
+def stage_forms(nx, ny, nz, opts=None):
+    """The kernel form of every stage on one grid; opts: {option: bool} of switches() (None: all on).  Priority: the order of each chain."""
+    sw = switches(None) if opts is None else opts
+    fold, fused = sw["fold"], (nx, nz) in XZ2D_SHAPES and sw["fused_xz"]
+    folds = lambda a, b: fold and a == b and a in XZ2D_FOLD_N              # a square (a, b) plane on the radix-2 kernels
+    pair = (nx, nz) == (32, 32) and (64, 32) in XZ2D_SHAPES and ny % 2 == 0 and sw["fused_xz"]
+    quad = pair and ny % 4 == 0 and fold and 64 in XZ2D_FOLD_N and sw["quad"]
+    xz = "fold" if (fused and folds(nx, nz)) else "fused" if fused else "quad" if quad else "pair" if pair else "gemm"
+    axis4 = lambda n: n in SPECTRAL_AXIS_N and half_integer(n) and sw["axis_mfma"]
+    dense_y = ny in TOEPLITZ_NY and sw["dense_y"]
+    y = "spectrum" if not dense_y else "mfma" if (ny in SPECTRAL_Y_NY and sw["y_mfma"]) else "toeplitz"
+    y_two_term = "y2t" if ny in TOEPLITZ_Y2T_NY else "add" if ny in TOEPLITZ_ADD_NY else "separate"
+    fused_ss = xz == "fold" and dense_y                  # (any Toeplitz ny: the reduction in the inverse transform takes any plane count)
+    zx = nx == ny == nz == 64 and folds(ny, nx) and sw["z_fused"]
+    return Forms(xz=xz, x_axis4=axis4(nx), y=y, y_two_term=y_two_term, y3t=y == "mfma" and ny in SPECTRAL_Y3T_NY,
+                 y2s=fused_ss and y_two_term == "y2t" and sw["y2s"], fold=fold, ss="fused" if fused_ss else "stored", lattice_feed=fused_ss and ny >= 3,
+                 plane_yx="fold" if folds(ny, nx) else "fused" if (ny, nx) in XZ2D_SHAPES else "gemm",
+                 gram_x="fold" if folds(nx, nz) else "plain" if (nx, nz) == (64, 64) else "fold_lamdot" if (fold and nz <= 128) else "gemm",
+                 gram_y_axis4=axis4(ny), zx=zx, z_mul=zx and sw["z_mul"], ymul_slabs=tuple(k for m, k in YMUL_SHAPES if m == 2 * ny))
 
 
 def _pad(v, m):
@@ -84,6 +148,7 @@ class Route:
     ak_bytes: int = 0       # what a materialised A K (column form / one-rank fused form) of this rank would take
     rows_mandatory: bool = False   # ak_bytes > COLUMN_FORM_MAX_BYTES: only the row form fits; a denied row form is an error, not a fallback
     switches: tuple = ()    # ((option, bool), ...) of SWITCHES as resolved from the environment handed to plan_route
+    forms: object = None    # Forms: the record `kernels`, `single` and `rows` were derived from; what the spectral product and the lattice Gram run on
 
     def opt(self, name):
         return dict(self.switches).get(name, True)
@@ -126,23 +191,18 @@ def plan_route(nx, ny, nz, world=1, rank=0, assembly="f64", operators="resident"
     shards = [shard_columns(N_pad, world, r) for r in range(world)]
     aligned = all(c0 % plane == 0 and c1 % plane == 0 and c1 > c0 for c0, c1 in shards)
     spectral = (method in ("auto", "spectral") and nx % 16 == 0 and ny % 16 == 0 and nz % 16 == 0 and N == N_pad and aligned)
-    fused_xz = (nx, nz) in XZ2D_SHAPES and sw["fused_xz"]
-    pair_xz = (nx, nz) == (32, 32) and (64, 32) in XZ2D_SHAPES and ny % 2 == 0 and sw["fused_xz"]
-    fold = sw["fold"] and nx == nz and nx in XZ2D_FOLD_N
-    dense_y = ny in TOEPLITZ_NY and sw["dense_y"]
-    y_mfma = dense_y and ny in SPECTRAL_Y_NY and sw["y_mfma"]
-    fused_ss = fused_xz and fold and dense_y          # (any Toeplitz ny: the reduction in the inverse transform takes any plane count)
+    forms = stage_forms(nx, ny, nz, sw)
+    fused_ss, dense_y, fast_xz = forms.ss == "fused", forms.y != "spectrum", forms.xz in ("fold", "fused", "quad")
     transposed = env.get("GEOBO_POSTERIOR", "zpath") == "zpath"
     unpadded = Ms == Ms_pad and N == N_pad
     gram_ok = lattice_gram_supported(nx, ny, nz) and sw["aka_lattice"]
     gram_fast = lattice_gram_fast(nx, ny, nz)
     single = world == 1 and not f32 and spectral and unpadded and transposed and fused_ss
-    quad_xz = pair_xz and ny % 4 == 0 and sw["fold"] and 64 in XZ2D_FOLD_N and sw["quad"]
     rows_mode = env.get("GEOBO_ROWS", "auto")           # "0": never; "1": wherever it is possible; "auto": where it pays
     # a materialised A K of this rank: nprops property blocks in the element size of the assembly (fp32 assembly stores A K as fp32); the
     # engine repeats the check with the step's own property count where it allocates (engine._assemble_AK)
     column_ak_bytes = (2 * Ms_pad + PAD_M) * int(nprops) * N_pad * (4 if f32 else 8) // max(world, 1)
-    pays = ((gram_fast and fused_ss) or ((fused_xz or quad_xz) and dense_y and N >= ROWS_MIN_VOXELS_FUSED)
+    pays = ((gram_fast and fused_ss) or (fast_xz and dense_y and N >= ROWS_MIN_VOXELS_FUSED)
             or (N >= ROWS_MIN_VOXELS and plane >= ROWS_MIN_PLANE) or (N >= ROWS_MIN_VOXELS_MID and plane >= ROWS_MIN_PLANE_MID)
             or column_ak_bytes > COLUMN_FORM_MAX_BYTES)
     xmode = env.get("GEOBO_SPECTRAL_EXCHANGE", "auto")    # "0": replicated forward transforms, column shards (also switches the row form off for N > 1)
@@ -161,7 +221,7 @@ def plan_route(nx, ny, nz, world=1, rank=0, assembly="f64", operators="resident"
                          "modes (%d with %d) on the batched-GEMM forms (here %d x %d x %d: %d voxels, %d modes, %s (x, z) kernels): N-deep Gram "
                          "and fused reduction (2-6x the work of the structured forms at larger sizes)"
                          % (ROWS_MIN_VOXELS_FUSED, ROWS_MIN_VOXELS, ROWS_MIN_PLANE, ROWS_MIN_VOXELS_MID, ROWS_MIN_PLANE_MID, nx, ny, nz, N, plane,
-                            "fused" if (fused_xz or quad_xz) else "no fused"))
+                            "fused" if fast_xz else "no fused"))
         elif world > 1 and Ms % world:
             notes.append("%d sensor rows do not divide over %d ranks: column shards" % (Ms, world))
     if not spectral and method == "auto" and (nx % 16 or ny % 16 or nz % 16):
@@ -172,9 +232,7 @@ def plan_route(nx, ny, nz, world=1, rank=0, assembly="f64", operators="resident"
     if family == "rows" and not streamed and rows_r * N_pad * 8 > (40 << 30):
         ops = "streamed"
         notes.append("operator rows of a rank (%.0f GB) are generated per batch instead of being resident" % (rows_r * N_pad * 8 / 1e9))
-    kernels = (("xz", "fold" if (fused_xz and fold) else "fused" if fused_xz else "quad" if quad_xz else "pair" if pair_xz else
-                "gemm+axis4" if (nx in SPECTRAL_AXIS_N and sw["axis_mfma"]) else "gemm"),
-               ("y", ("mfma" if y_mfma else "toeplitz") if dense_y else "spectrum"),
+    kernels = (("xz", "gemm+axis4" if (forms.xz == "gemm" and forms.x_axis4) else forms.xz), ("y", forms.y),
                ("gram", ("fused" if gram_fast else "gemm") if (family in ("rows", "single") and gram_ok) else "per-step"),
                ("ss", ("fused" if fused_ss else "stored") if family in ("rows", "single") else "reduction"))
     if column_ak_bytes > COLUMN_FORM_MAX_BYTES and family != "rows":
@@ -182,4 +240,4 @@ def plan_route(nx, ny, nz, world=1, rank=0, assembly="f64", operators="resident"
                      % (column_ak_bytes / 1e9, COLUMN_FORM_MAX_BYTES / 1e9, "switched off (GEOBO_ROWS=0)" if rows_mode == "0" else "not available here"))
     return Route(spectral=spectral, family=family, rows=rows, single=single, exchange=exchange, exchange_without_rows=exchange_without_rows,
                  operators=ops, kernels=kernels, note="; ".join(notes), ak_bytes=int(column_ak_bytes),
-                 rows_mandatory=bool(column_ak_bytes > COLUMN_FORM_MAX_BYTES), switches=tuple(sorted(sw.items())))
+                 rows_mandatory=bool(column_ak_bytes > COLUMN_FORM_MAX_BYTES), switches=tuple(sorted(sw.items())), forms=forms)

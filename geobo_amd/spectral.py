@@ -23,7 +23,8 @@ import os
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, plan
+from .plan import INTEGER_BASIS_N, half_integer  # noqa: F401  (the basis of an extent is the planner's table; re-exported here)
 
 F64 = hip.F64
 SLACK = 4096  # doubles of slack behind every buffer: compute tiles may overhang the valid region (reads only)
@@ -51,20 +52,6 @@ def base_modes(n):
     for om in range(1, q):
         modes += [("cos", om), ("sin", om), ("cos", n // 2 - om), ("sin", n // 2 - om)]
     return modes
-
-
-INTEGER_BASIS_N = (32, 64)      # extents whose fused kernels (xz2d_fold.hip: n = 64, and the four-plane form of 32 x 32 planes) build the
-                                # integer-frequency basis of base_modes() internally; every other extent takes the half-integer basis below
-
-
-def half_integer(n):
-    """True where the axis runs on the HALF-INTEGER (skew-circulant) basis (round 6): a symmetric Toeplitz block of size n is also the
-    leading block of the skew-circulant of size P = 2n (first column k_0 .. k_{n-1}, *, -k_{n-1} .. -k_1), diagonalised by cos / sin of
-    the frequencies kappa = 1/2 .. n - 1/2 with eigenvalues sum_d w_d k(d) cos(2 pi kappa d / P).  No frequency is its own mirror or
-    quarter-period image, so all n frequencies fall into n/4 orbits {kappa, n - kappa, n/2 + kappa, n/2 - kappa} of ONE shape -- what
-    the radix-4 axis kernels of spectral_y.hip want.  Every consumer of G / G^T / E treats the spectral index as opaque (the eigen-data
-    go through the same matrices), and the pair structure row 2b+1 = (-1)^i row 2b of the radix-2 passes holds for every pair."""
-    return n not in INTEGER_BASIS_N
 
 
 def half_modes(n):
@@ -169,43 +156,27 @@ class LatticeRows:
 class SpectralProduct:
     """AK rows by the real-DFT route for one grid; holds the transform matrices and the work buffers."""
 
-    def __init__(self, nx, ny, nz, device, rows_per_batch=None, plane_pad=0, opts=None):
+    def __init__(self, nx, ny, nz, device, rows_per_batch=None, plane_pad=0, opts=None, forms=None):
         if nx % 16 or ny % 16 or nz % 16:
             raise ValueError("spectral path needs grid extents that are multiples of 16")
         self.nx, self.ny, self.nz = nx, ny, nz
-        # behaviour switches: resolved ONCE by the planner (plan.switches; the engine hands its route's options in); a product built on
-        # its own (tests, tools) asks the planner with the process environment
-        from . import plan
-        self.opts = dict(plan.switches(os.environ)) if opts is None else dict(opts)
+        # which kernel form carries each stage: decided ONCE by the planner (plan.stage_forms; the engine hands its route's record in); a
+        # product built on its own (tests, tools) asks the planner, with the process environment unless `opts` (plan.switches) are given
+        self.forms = f = forms or plan.stage_forms(nx, ny, nz, plan.switches(os.environ) if opts is None else opts)
         self.Px, self.Py, self.Pz = 2 * nx, 2 * ny, 2 * nz
-        self.N = nx * ny * nz
-        self.P3 = self.Px * self.Py * self.Pz
+        self.N, self.P3 = nx * ny * nz, self.Px * self.Py * self.Pz
         self.device = device
         dev = lambda a: hip.to_dev(a, device)
-        self.G = {a: dev(_pad_rows(forward_matrix(n))) for a, n in (("x", nx), ("y", ny), ("z", nz))}
-        self.GT = {a: dev(_pad_rows(forward_matrix(n).T.copy())) for a, n in (("x", nx), ("y", ny), ("z", nz))}
-        self.E = {a: dev(_pad_rows(eigen_matrix(n))) for a, n in (("x", nx), ("y", ny), ("z", nz))}
-        # folded (radix-2) matrices [n][n/2][(Fe, Fo)] for the axes the radix-2 kernels are instantiated for
-        self.F = {a: dev(np.stack(folded_matrices(n), axis=2)) for a, n in (("x", nx), ("y", ny), ("z", nz)) if n in hip.XZ2D_FOLD_N}
-        self.fold = self.opts["fold"]
-        # y axis: applied as Toeplitz blocks per (x, z) mode (geobo_toeplitz_y) when the kernel has the extent, else carried
-        # through the spectrum like x and z
-        self.dense_y = ny in hip.TOEPLITZ_NY and self.opts["dense_y"]
-        # ... and, where instantiated, through the y axis's own spectrum INSIDE the kernel, on the matrix pipe (round 6: geobo_spectral_y,
-        # same arguments, same sums to rounding; GEOBO_Y_MFMA=0 keeps the direct vector-pipe kernels: the A/B of profiles/r06_*)
-        self.y_mfma = self.dense_y and ny in hip.SPECTRAL_Y_NY and self.opts["y_mfma"]
-        # x passes of the unfused (x, z) transforms: radix-4 axis kernels on the half-integer basis (geobo_spectral_axis) where instantiated
-        self.x_mfma = self.axis_mfma(nx)
-        # x and z: one fused kernel per direction (geobo_xz2d) where it is instantiated, else two batched GEMM passes
-        self.fused_xz = (nx, nz) in hip.XZ2D_SHAPES and self.opts["fused_xz"]
-        # 32 x 32 planes: two consecutive y-planes stacked along x go through the (64, 32) instance with diag(Mx, Mx) -- the z step
-        # is row-wise anyway, the x step spends half its MFMAs on the zero blocks (cheap next to two GEMM passes through HBM)
-        self.pair_xz = (nx, nz) == (32, 32) and (64, 32) in hip.XZ2D_SHAPES and ny % 2 == 0 and self.opts["fused_xz"]
-        # 32 x 32 planes, better: FOUR consecutive y-planes as one 64 x 64 plane of the radix-2 kernels with the folded matrices of
-        # diag(G32, G32) (geobo_xz2d_fold_quad): no zero blocks in z, folded in both axes, four waves per workgroup
-        self.quad_xz = ((nx, nz) == (32, 32) and ny % 4 == 0 and 64 in hip.XZ2D_FOLD_N and self.fold
-                        and self.opts["quad"] and self.opts["fused_xz"])
-        if self.quad_xz:
+        axes = {"x": nx, "y": ny, "z": nz}
+        self.G = {a: dev(_pad_rows(forward_matrix(n))) for a, n in axes.items()}
+        self.GT = {a: dev(_pad_rows(forward_matrix(n).T.copy())) for a, n in axes.items()}
+        self.E = {a: dev(_pad_rows(eigen_matrix(n))) for a, n in axes.items()}
+        # folded (radix-2) matrices [n][n/2][(Fe, Fo)] of the axes whose stages run on the radix-2 kernels
+        self.F = {a: dev(np.stack(folded_matrices(axes[a]), axis=2)) for a in f.folded_axes()}
+        # 32 x 32 planes, "pair": two consecutive y-planes stacked along x through the (64, 32) instance with diag(Mx, Mx) (_paired): the z step
+        # is row-wise anyway, the x step spends half its MFMAs on the zero blocks (cheap next to two GEMM passes through HBM); "quad": FOUR
+        # y-planes as one 64 x 64 plane of the radix-2 kernels with the folded matrices of diag(G32, G32): no zero blocks in z, folded in both axes
+        if f.xz == "quad":
             fe, fo = folded_matrices(32)
             fq = np.zeros((64, 32, 2))
             fq[:32, :16, 0], fq[:32, :16, 1] = fe, fo
@@ -218,12 +189,9 @@ class SpectralProduct:
         # pipeline do not move: toeplitz_y 1.514 / 1.506 ms, inverse transform 0.372 / 0.375 ms, forward 0.571 / 0.573 ms with / without
         # the padding (profiles/r03_spectral_plane_pad_ab.txt): they are held by the fp64 VALU / the matrix pipe at the clock a
         # memory-bound launch runs at, not by channel aliasing.  The stride stays a parameter (`plane_pad`, doubles; the A/B switch
-        # of round 3 is retired); default dense.  Fused kernels only: they take explicit row / plane strides.
-        C = self.Px * self.Pz
-        pad = int(plane_pad)
+        # of round 3 is retired); default dense.  Fused kernels with the in-kernel y stage only (explicit strides); elsewhere Cp = Px*Pz.
+        C, pad = self.Px * self.Pz, int(plane_pad)
         self.Cp = C + pad if (self.fused_xz and self.dense_y and C % 2048 == 0 and pad > 0) else C
-        # operator rows fed straight from a lattice survey's stencil table (LatticeRows): needs the radix-2 forward kernel
-        self.lattice_feed = self.fused_xz and self.fold and nx == nz and "x" in self.F and ny >= 3 and self.dense_y
         if rows_per_batch is None:
             per_row = (ny * self.Cp if self.dense_y else self.P3) * 8
             # ~3 GB per work buffer; ny = 128 (67 MB of spectrum per row): 48 rows.  Measured on the 128^3 rank step with the round-4 y
@@ -236,9 +204,10 @@ class SpectralProduct:
         self._bufs = {}
         self.kernel_timer = None     # callable(name, algorithmic_bytes, fn) -> fn(): the engine's HIP-event bracket for single kernels
 
-    def axis_mfma(self, n):
-        """True where a pass along a strided axis of extent n runs as a radix-4 axis kernel (geobo_spectral_axis)."""
-        return n in hip.SPECTRAL_AXIS_N and half_integer(n) and self.opts.get("axis_mfma", True)
+    # y per (x, z) mode inside one kernel (geobo_toeplitz_y), not by passes like x and z; there on the matrix pipe (round 6: geobo_spectral_y, same sums to rounding)
+    dense_y = property(lambda self: self.forms.y != "spectrum")
+    y_mfma = property(lambda self: self.forms.y == "mfma")
+    fused_xz = property(lambda self: self.forms.xz in ("fold", "fused"))     # x and z of one whole plane inside one kernel (radix-2 or plain)
 
     def _ystage(self, ny, C, R, src, tabs, outs, y0, y1, plane, accumulate=False):
         """geobo_toeplitz_y launch, bracketed for the bench's per-kernel roofline when a timer is set: algorithmic bytes = the rows'
@@ -250,12 +219,15 @@ class SpectralProduct:
             fn = lambda: hip.spectral_y(ny, C, R, src, tabs, outs, y0, y1, plane=plane, accumulate=accumulate)
         else:
             fn = lambda: hip.toeplitz_y(ny, C, R, src, tabs, outs, y0, y1, plane=plane, accumulate=accumulate)
-        if self.kernel_timer is None:
-            return fn()
         # (one name per kernel symbol: single-block launches run toeplitz_y_kernel<ny, 2>, the others <ny, 1>)
         name = "kernel:toeplitz_y" if len(tabs) >= 2 or ny > 64 else "kernel:toeplitz_y_single"
-        fl, fv = self.y_stage_flop(1, len(tabs), y1 - y0)
-        return self.kernel_timer(name, 8.0 * R * C * (ny + (2 if accumulate else 1) * len(tabs) * (y1 - y0)), fn, valu=R * fv, flop=R * fl)
+        return self._launch(name, 8.0 * R * C * (ny + (2 if accumulate else 1) * len(tabs) * (y1 - y0)), R, self.y_stage_flop(1, len(tabs), y1 - y0), fn)
+
+    def _launch(self, name, nbytes, rows, flop, fn):
+        """fn(), bracketed by the engine's per-kernel timer when one is set; flop: (executed, its vector-pipe part) per row."""
+        if self.kernel_timer is None:
+            return fn()
+        return self.kernel_timer(name, nbytes, fn, valu=rows * flop[1], flop=rows * flop[0])
 
     def buf(self, name, n):
         b = self._bufs.get(name)
@@ -278,39 +250,30 @@ class SpectralProduct:
     def forward_zx(self, src, R, M, src_row_stride=None, out_name="T2"):
         """src: R volumes of ny*nx*nz doubles, `src_row_stride` doubles apart (default: contiguous)."""
         nx, ny, nz, Px, Pz, Cp = self.nx, self.ny, self.nz, self.Px, self.Pz, self.Cp
-        rows = R * ny * nx
+        xz, analysis = self.forms.xz, M is self.G      # (the radix-2 forms hold G in their folded matrices: the eigen-matrices E take the plain twins)
         lds = self.N if src_row_stride is None else int(src_row_stride)
-        if isinstance(src, LatticeRows):
-            assert self.lattice_feed and M is self.G
-            t2 = self.buf(out_name, R * ny * Cp)
+        t2 = self.buf(out_name, R * ny * Cp)           # planes Cp >= Px*Pz doubles apart (padded: see __init__)
+        if isinstance(src, LatticeRows):               # operator rows read from the survey's stencil table by the radix-2 forward kernel
+            assert self.forms.lattice_feed and analysis
             hip.xz2d_fold_lattice(nx, R, ny, src.Q, src.row_off[src.r0:], src.q_plane, src.edge[src.r0:], src.edge.stride(0),
                                   self.F["x"], self.F["z"], t2, ny * Cp, Cp)
-            return t2
-        if self.fused_xz:
-            t2 = self.buf(out_name, R * ny * Cp)       # planes Cp >= Px*Pz doubles apart (padded: see __init__)
-            if self.fold and M is self.G and nx == nz and "x" in self.F:     # radix-2 kernels: half the MFMAs (xz2d_fold.hip)
-                hip.xz2d_fold(False, nx, R, ny, src, lds, nx * nz, self.F["x"], self.F["z"], t2, ny * Cp, Cp)
-            else:
-                hip.xz2d(False, nx, nz, R, ny, src, lds, nx * nz, M["x"], M["z"], t2, ny * Cp, Cp)
-            return t2
-        if self.quad_xz and M is self.G:
-            t2 = self.buf(out_name, R * ny * Px * Pz)
-            hip.xz2d_fold_quad(False, nx, R, ny // 4, src, lds, nx * nz, self.Fq, self.Fq, t2, ny * Px * Pz, Px * Pz)
-            return t2
-        if self.pair_xz:
-            t2 = self.buf(out_name, R * ny * Px * Pz)
-            hip.xz2d(False, 2 * nx, nz, R, ny // 2, src, lds, 2 * nx * nz, self._paired(M["x"], Px, nx), M["z"], t2, ny * Px * Pz,
-                     2 * Px * Pz)
-            return t2
-        # any other extent: two batched passes, radix-2 (geobo_gemm_fold: half the multiply-adds) against the pair-interleaved basis
-        fold = self.fold and M is self.G
-        t1 = self.buf("T1", rows * Pz)
-        hip.axis_pass(fold, False, False, hip.pad_n(ny * nx), hip.pad_n(Pz), nz, src, nz, lds, M["z"], nz, 0, t1, Pz, ny * nx * Pz, ny * nx, Pz, R)
-        t2 = self.buf(out_name, R * ny * Px * Pz)
-        if self.x_mfma and M is self.G and Pz % 16 == 0:
-            hip.spectral_axis(False, nx, Pz, Pz, Pz, nx * Pz, Px * Pz, R * ny, t1, t2)
+        elif xz == "fold" and analysis:                # radix-2 kernels: half the MFMAs (xz2d_fold.hip)
+            hip.xz2d_fold(False, nx, R, ny, src, lds, nx * nz, self.F["x"], self.F["z"], t2, ny * Cp, Cp)
+        elif xz in ("fold", "fused"):
+            hip.xz2d(False, nx, nz, R, ny, src, lds, nx * nz, M["x"], M["z"], t2, ny * Cp, Cp)
+        elif xz == "quad" and analysis:
+            hip.xz2d_fold_quad(False, nx, R, ny // 4, src, lds, nx * nz, self.Fq, self.Fq, t2, ny * Cp, Cp)
+        elif xz in ("quad", "pair"):
+            hip.xz2d(False, 2 * nx, nz, R, ny // 2, src, lds, 2 * nx * nz, self._paired(M["x"], Px, nx), M["z"], t2, ny * Cp, 2 * Cp)
         else:
-            hip.axis_pass(fold, True, False, hip.pad_n(Px), hip.pad_n(Pz), nx, M["x"], nx, 0, t1, Pz, nx * Pz, t2, Pz, Px * Pz, Px, Pz, R * ny)
+            # any other extent: two batched passes, radix-2 (geobo_gemm_fold: half the multiply-adds) against the pair-interleaved basis
+            fold = self.forms.fold and analysis
+            t1 = self.buf("T1", R * ny * nx * Pz)
+            hip.axis_pass(fold, False, False, hip.pad_n(ny * nx), hip.pad_n(Pz), nz, src, nz, lds, M["z"], nz, 0, t1, Pz, ny * nx * Pz, ny * nx, Pz, R)
+            if self.forms.x_axis4 and analysis and Pz % 16 == 0:
+                hip.spectral_axis(False, nx, Pz, Pz, Pz, nx * Pz, Px * Pz, R * ny, t1, t2)
+            else:
+                hip.axis_pass(fold, True, False, hip.pad_n(Px), hip.pad_n(Pz), nx, M["x"], nx, 0, t1, Pz, nx * Pz, t2, Pz, Px * Pz, Px, Pz, R * ny)
         return t2
 
     def forward(self, src, R, M, out_name="T3", src_row_stride=None):
@@ -334,38 +297,33 @@ class SpectralProduct:
     def backward_xz(self, u2, R, ylo, yhi, targets):
         """u2: [R][yhi-ylo][Px][Pz] (y already in the space domain).  x pass over every (row, y), then one z pass per target
         (ya, yb, out, ldo): rows of `out` receive the y-slab [ya, yb) of every row."""
-        nx, nz, Px, Pz = self.nx, self.nz, self.Px, self.Pz
-        Ly = yhi - ylo
-        if self.fused_xz:
-            Cp = self.Cp if self.dense_y else Px * Pz       # (y through the spectrum: the batched GEMM of backward() writes dense planes)
+        nx, nz, Px, Pz, Cp = self.nx, self.nz, self.Px, self.Pz, self.Cp
+        Ly, xz = yhi - ylo, self.forms.xz
+        whole = lambda k: all((yb - ya) % k == 0 for ya, yb, _, _ in targets)      # every slab is a whole number of k-plane groups
+        if xz == "fold":
             for ya, yb, out, ldo in targets:
-                if self.fold and nx == nz and "x" in self.F:
-                    hip.xz2d_fold(True, nx, R, yb - ya, u2[(ya - ylo) * Cp:], Ly * Cp, Cp, self.F["x"], self.F["z"],
-                                  out, ldo, nx * nz)
-                else:
-                    hip.xz2d(True, nx, nz, R, yb - ya, u2[(ya - ylo) * Cp:], Ly * Cp, Cp, self.GT["x"], self.GT["z"],
-                             out, ldo, nx * nz)
-            return
-        if self.quad_xz and all((yb - ya) % 4 == 0 for ya, yb, _, _ in targets):
+                hip.xz2d_fold(True, nx, R, yb - ya, u2[(ya - ylo) * Cp:], Ly * Cp, Cp, self.F["x"], self.F["z"], out, ldo, nx * nz)
+        elif xz == "fused":
             for ya, yb, out, ldo in targets:
-                hip.xz2d_fold_quad(True, nx, R, (yb - ya) // 4, u2[(ya - ylo) * Px * Pz:], Ly * Px * Pz, Px * Pz, self.Fq, self.Fq,
-                                   out, ldo, nx * nz)
-            return
-        if self.pair_xz and all((yb - ya) % 2 == 0 for ya, yb, _, _ in targets):
+                hip.xz2d(True, nx, nz, R, yb - ya, u2[(ya - ylo) * Cp:], Ly * Cp, Cp, self.GT["x"], self.GT["z"], out, ldo, nx * nz)
+        elif xz == "quad" and whole(4):
             for ya, yb, out, ldo in targets:
-                hip.xz2d(True, 2 * nx, nz, R, (yb - ya) // 2, u2[(ya - ylo) * Px * Pz:], Ly * Px * Pz, 2 * Px * Pz,
+                hip.xz2d_fold_quad(True, nx, R, (yb - ya) // 4, u2[(ya - ylo) * Cp:], Ly * Cp, Cp, self.Fq, self.Fq, out, ldo, nx * nz)
+        elif xz in ("quad", "pair") and whole(2):
+            for ya, yb, out, ldo in targets:
+                hip.xz2d(True, 2 * nx, nz, R, (yb - ya) // 2, u2[(ya - ylo) * Cp:], Ly * Cp, 2 * Cp,
                          self._paired(self.GT["x"], nx, Px), self.GT["z"], out, ldo, 2 * nx * nz)
-            return
-        u1 = self.buf("U1", R * Ly * nx * Pz)
-        if self.x_mfma and Pz % 16 == 0:
-            hip.spectral_axis(True, nx, Pz, Pz, Pz, Px * Pz, nx * Pz, R * Ly, u2, u1)
         else:
-            hip.axis_pass(self.fold, True, True, hip.pad_n(nx), hip.pad_n(Pz), Px, self.GT["x"], Px, 0, u2, Pz, Px * Pz, u1, Pz, nx * Pz, nx, Pz,
-                          R * Ly)
-        for ya, yb, out, ldo in targets:
-            slab = yb - ya
-            hip.axis_pass(self.fold, False, True, hip.pad_n(slab * nx), hip.pad_n(nz), Pz, u1[(ya - ylo) * nx * Pz:], Pz, Ly * nx * Pz,
-                          self.GT["z"], Pz, 0, out, nz, ldo, slab * nx, nz, R)
+            fold = self.forms.fold
+            u1 = self.buf("U1", R * Ly * nx * Pz)
+            if self.forms.x_axis4 and Pz % 16 == 0:
+                hip.spectral_axis(True, nx, Pz, Pz, Pz, Px * Pz, nx * Pz, R * Ly, u2, u1)
+            else:
+                hip.axis_pass(fold, True, True, hip.pad_n(nx), hip.pad_n(Pz), Px, self.GT["x"], Px, 0, u2, Pz, Px * Pz, u1, Pz, nx * Pz, nx, Pz, R * Ly)
+            for ya, yb, out, ldo in targets:
+                slab = yb - ya
+                hip.axis_pass(fold, False, True, hip.pad_n(slab * nx), hip.pad_n(nz), Pz, u1[(ya - ylo) * nx * Pz:], Pz, Ly * nx * Pz,
+                              self.GT["z"], Pz, 0, out, nz, ldo, slab * nx, nz, R)
 
     def flops(self, rows, nblocks, slab):
         """Executed flop of product(): forward passes once, the rest per property block (compute extents)."""
@@ -373,15 +331,16 @@ class SpectralProduct:
         pn = hip.pad_n
         fwd = 2.0 * (ny * nx * pn(Pz) * nz + ny * pn(Px) * pn(Pz) * nx)
         bwd = 2.0 * (slab * pn(nx) * pn(Pz) * Px + pn(slab * nx) * pn(nz) * Pz)
-        if self.fold and not (self.fused_xz or self.quad_xz or self.pair_xz):
+        xz = self.forms.xz
+        if xz == "gemm" and self.forms.fold:
             fwd, bwd = 0.5 * fwd, 0.5 * bwd         # radix-2 batched passes (geobo_gemm_fold)
-        if self.quad_xz:                            # four planes per 64-point radix-2 plane: folded, both axes over the zero blocks
+        elif xz == "quad":                          # four planes per 64-point radix-2 plane: folded, both axes over the zero blocks
             fwd = 0.25 * ny * (64.0 * 64 * 128 + 128.0 * 64 * 128)
             bwd = 0.25 * slab * (128.0 * 128 * 64 + 64.0 * 128 * 64)
-        elif self.pair_xz:                          # diag(Mx, Mx) on stacked plane pairs: the x steps run over the zero blocks too
+        elif xz == "pair":                          # diag(Mx, Mx) on stacked plane pairs: the x steps run over the zero blocks too
             fwd += 2.0 * ny * Px * Pz * nx
             bwd += 2.0 * slab * nx * Pz * Px
-        if self.fused_xz and self.fold and "x" in self.F and nx == nz:
+        elif xz == "fold":
             # radix-2 / radix-4 kernels (xz2d_fold.hip): forward z step one even- and one odd-input sum per spectral pair (half the plain
             # multiply-adds), forward x step and both inverse steps one cos / sin row per frequency group and residue class (a quarter)
             fwd = 2.0 * ny * (0.5 * nx * pn(Pz) * nz + 0.25 * pn(Px) * pn(Pz) * nx)
@@ -422,8 +381,7 @@ class SpectralProduct:
         src = self.buf("Tsrc", self.N)
         src[:self.N] = T.reshape(-1)
         if self.dense_y:
-            C = self.Px * self.Pz
-            Cp = self.Cp if self.fused_xz else C          # plane stride of what forward_zx wrote
+            C, Cp = self.Px * self.Pz, self.Cp            # (Cp: plane stride of what forward_zx wrote)
             gen = self.forward_zx(src, 1, self.E, out_name="Lam")[:ny * Cp].view(ny, Cp)[:, :C].clone().view(-1)   # own dense [ny][C] table (the work buffer is reused)
             gen.mul_(1.0 / float(C))
             return gen
@@ -441,7 +399,7 @@ class SpectralProduct:
             slabs = [(y0, y1, outs)]
         N = self.N
         if isinstance(A, LatticeRows):
-            assert self.lattice_feed
+            assert self.forms.lattice_feed
         else:
             assert A.stride(1) == 1 and A.stride(0) >= N and A.stride(0) % 2 == 0
         if self.dense_y:
@@ -468,8 +426,7 @@ class SpectralProduct:
 
     def _product_dense_y(self, A, Ms, gens, slabs):
         """z and x through the spectrum, y as Toeplitz blocks: one read of the (x, z)-spectrum per pair of property blocks."""
-        ny, C = self.ny, self.Px * self.Pz
-        Cp = self.Cp if self.fused_xz else C
+        ny, C, Cp = self.ny, self.Px * self.Pz, self.Cp
         ylo, yhi = min(s[0] for s in slabs), max(s[1] for s in slabs)
         n_out = (yhi - ylo) * Cp
         for r0 in range(0, Ms, self.R):
@@ -489,7 +446,7 @@ class SpectralProduct:
     def fused_ss(self):
         """True where the inverse transform itself squares and sums its output planes (geobo_xz2d_fold_inv_ss: the radix-2 kernels of
         nx = nz = 64 with the Toeplitz y stage); elsewhere reduce_ss stores a batch of V rows and geobo_sumsq_accum reduces it."""
-        return self.fused_xz and self.fold and self.nx == self.nz and "x" in self.F and self.dense_y
+        return self.forms.ss == "fused"
 
     GENERIC_SS_SLOTS = 8
 
@@ -505,8 +462,7 @@ class SpectralProduct:
         synchronisation (engine.posterior raises above 1e-12).  Returns (a, D0 = gens_g[a] - X, X = gens_g[b], D1 = gens_m[b] - X)."""
         self.sym_residual = None
         a, b = pair
-        if not (self.fused_ss() and self.ny in hip.TOEPLITZ_Y2T_NY and b == a + 1 and a % 2 == 0 and b < len(gens_g)
-                and self.opts["y2s"]):
+        if not (self.forms.y2s and b == a + 1 and a % 2 == 0 and b < len(gens_g)):
             return None
         x = gens_g[b]
         # (cross weight 0 -- gp_coeff = [.., .., 0], a legal prior -- makes both cross blocks exactly zero: 0 / 0 must not read as
@@ -525,14 +481,13 @@ class SpectralProduct:
         y2s: tables of y2s_tables() for a pair of blocks whose cross blocks coincide -- the two-term rows of that pair then cost three
         y-stage products instead of four (geobo_toeplitz_y2s)."""
         nx, ny, nz, C, Cp, R = self.nx, self.ny, self.nz, self.Px * self.Pz, self.Cp, self.R
-        P_c = len(gens_g)
-        y2s_tabs = y2s
+        P_c, y2s_tabs, meet = len(gens_g), y2s, self.forms.y_two_term     # meet: how the two terms of a row come together in the y stage
         if Zm is None:
             m_first = Mg
         starts = list(range(0, min(m_first, Mg), R)) + list(range(m_first, Mg, R))
         if not self.fused_ss():
             N = self.N
-            add_y = self.dense_y and ny in hip.TOEPLITZ_ADD_NY
+            add_y = self.dense_y and meet == "add"
             for r0 in starts:
                 two = r0 >= m_first
                 Rb = min(R, (Mg if two else min(m_first, Mg)) - r0)
@@ -540,24 +495,19 @@ class SpectralProduct:
                 if two and add_y:
                     # both terms meet in the (x, z)-spectrum: the second y stage adds into the first one's output, ONE inverse
                     # transform per block instead of two (what geobo_toeplitz_y2t does for the register-table kernel)
-                    Cq = Cp if self.fused_xz else C
                     t2g = self.forward_zx(Zg[r0:], Rb, self.G, src_row_stride=Zg.stride(0), out_name="T2")
                     t2m = self.forward_zx(Zm[r0 - m_first:], Rb, self.G, src_row_stride=Zm.stride(0), out_name="T2b")
                     for j in range(0, P_c, 3):
                         js = list(range(j, min(j + 3, P_c)))
-                        u2 = [self.buf(("S", "S1", "S2")[i], Rb * ny * Cq) for i in range(len(js))]
-                        if self.y_mfma and ny in hip.SPECTRAL_Y3T_NY:
+                        u2 = [self.buf(("S", "S1", "S2")[i], Rb * ny * Cp) for i in range(len(js))]
+                        if self.forms.y3t:
                             # both terms in ONE pass, meeting in the y spectrum (geobo_spectral_y3t): 2 + len(js) transforms instead of
                             # 2 (1 + len(js)), no read-modify-write of the outputs
-                            fn = lambda: hip.spectral_y3t(ny, C, Rb, t2g, t2m, [gens_g[jj] for jj in js], [gens_m[jj] for jj in js], u2, plane=Cq)
-                            if self.kernel_timer is None:
-                                fn()
-                            else:
-                                fl, fv = self.y_stage_flop(2, len(js))
-                                self.kernel_timer("kernel:toeplitz_y", 8.0 * Rb * C * ny * (2 + len(js)), fn, valu=Rb * fv, flop=Rb * fl)
+                            fn = lambda: hip.spectral_y3t(ny, C, Rb, t2g, t2m, [gens_g[jj] for jj in js], [gens_m[jj] for jj in js], u2, plane=Cp)
+                            self._launch("kernel:toeplitz_y", 8.0 * Rb * C * ny * (2 + len(js)), Rb, self.y_stage_flop(2, len(js)), fn)
                         else:
-                            self._ystage(ny, C, Rb, t2g, [gens_g[jj] for jj in js], u2, 0, ny, Cq)
-                            self._ystage(ny, C, Rb, t2m, [gens_m[jj] for jj in js], u2, 0, ny, Cq, accumulate=True)
+                            self._ystage(ny, C, Rb, t2g, [gens_g[jj] for jj in js], u2, 0, ny, Cp)
+                            self._ystage(ny, C, Rb, t2m, [gens_m[jj] for jj in js], u2, 0, ny, Cp, accumulate=True)
                         for i, jj in enumerate(js):
                             self.backward_xz(u2[i], Rb, 0, ny, [(0, ny, vg[jj], vg[jj].stride(0))])
                     for jj in range(P_c):
@@ -579,7 +529,7 @@ class SpectralProduct:
             for j in range(0, P_c, 2):
                 js = list(range(j, min(j + 2, P_c)))
                 sg = [self.buf(("S", "S1")[i], Rb * ny * Cp) for i in range(len(js))]
-                if two and len(js) == 2 and ny in hip.TOEPLITZ_Y2T_NY:
+                if two and len(js) == 2 and meet == "y2t":
                     # both terms in ONE y-stage pass: one output spectrum per block, one input of the inverse; with the shared cross
                     # block three products per mode (geobo_toeplitz_y2s), otherwise four (geobo_toeplitz_y2t)
                     if y2s_tabs is not None and y2s_tabs[0] == j:
@@ -589,17 +539,13 @@ class SpectralProduct:
                     else:
                         fn = lambda: hip.toeplitz_y2t(ny, C, Rb, t2g, t2m, [gens_g[jj] for jj in js], [gens_m[jj] for jj in js], sg, plane=Cp)
                         kname, nprod = "kernel:toeplitz_y2t", 4
-                    if self.kernel_timer is None:
-                        fn()
-                    else:
-                        self.kernel_timer(kname, 8.0 * Rb * C * (2 * ny + 2 * ny), fn, valu=Rb * self.y_stage_flop(2, 2, shared=nprod == 3)[1],
-                                          flop=Rb * self.y_stage_flop(2, 2, shared=nprod == 3)[0])
+                    self._launch(kname, 8.0 * Rb * C * (2 * ny + 2 * ny), Rb, self.y_stage_flop(2, 2, shared=nprod == 3), fn)
                     for i, jj in enumerate(js):
                         hip.xz2d_fold_inv_ss(nx, Rb, ny, sg[i], ny * Cp, Cp, self.F["x"], self.F["z"], ss[jj])
                     continue
                 self._ystage(ny, C, Rb, t2g, [gens_g[jj] for jj in js], sg, 0, ny, Cp)
                 sm = None
-                if two and ny in hip.TOEPLITZ_ADD_NY:
+                if two and meet == "add":
                     self._ystage(ny, C, Rb, t2m, [gens_m[jj] for jj in js], sg, 0, ny, Cp, accumulate=True)     # the terms meet in the spectrum
                 elif two:
                     sm = [self.buf(("Sb", "S1b")[i], Rb * ny * Cp) for i in range(len(js))]

@@ -1,4 +1,6 @@
 """Kernel-level parity of the HIP path (through the C ABI) against torch fp64 / the oracle.  GPU only."""
+import dataclasses
+
 import numpy as np
 import pytest
 import torch
@@ -1017,10 +1019,12 @@ def test_lattice_transposed_application_matches_the_gemm(hip, ny, nrows, monkeyp
             print("  fused (zx layout): %.2e" % err2)
             assert err2 <= 1e-12
             # the product W = Lambda * lhat formed inside the inverse kernel (default) against W written and read back: same arithmetic
-            gram.sp.opts["z_mul"] = False               # (the option GEOBO_Z_MUL=0 resolves to: plan.SWITCHES)
+            planned = gram.sp.forms
+            assert planned.z_mul
+            gram.sp.forms = dataclasses.replace(planned, z_mul=False)     # (what GEOBO_Z_MUL=0 plans: plan.stage_forms)
             out3 = torch.full((nrows, N + 16), float("nan"), dtype=torch.float64, device="cuda")[:, :N]
             gram.apply_transpose_zx(Lv, nrows, gram.transpose_tables3(lam), out3)
-            gram.sp.opts["z_mul"] = True
+            gram.sp.forms = planned
             pl2 = slice(pl, N - pl)                     # (the boundary slabs of out2 were overwritten above)
             dev = (out3[:, pl2] - out2[:, pl2]).abs().max().item() / out2[:, pl2].abs().max().item()
             assert dev <= 1e-14                        # (the k-steps of the first contraction are summed in two chains there, four here)
@@ -1059,28 +1063,57 @@ def test_a_sens_slab_origin_is_validated_by_the_library(hip):
 
 @pytest.mark.parametrize("R,ny", [(3, 32), (5, 16)])
 def test_spectral_32_planes_go_through_the_fused_kernel_in_pairs(hip, R, ny):
-    """32 x 32 planes (BASELINE config 2): two y-planes stacked along x through the (64, 32) instance with diag(Mx, Mx), against
-    the two batched GEMM passes the same class falls back to."""
+    """32 x 32 planes (BASELINE config 2): two y-planes stacked along x through the (64, 32) instance with diag(Mx, Mx) ("pair") and,
+    at ny = 32, four y-planes as one 64 x 64 plane of the radix-2 kernels ("quad"), each against the two batched GEMM passes the same
+    class falls back to ("gemm"), forward and inverse.  The form is selected by replacing the record's `xz`: both grids plan "quad",
+    which used to shadow the pair kernel in this test (forward at ny % 4 == 0, inverse for slabs of whole plane quadruples)."""
     from geobo_amd.spectral import SpectralProduct
     sp = SpectralProduct(32, ny, 32, "cuda")
-    assert sp.pair_xz and not sp.fused_xz
+    planned = sp.forms
+    assert planned.xz == "quad"
     src = _rand((R, sp.N), 90 + R)
-    got = sp.forward_zx(src, R, sp.G, out_name="pair_fwd")[:R * ny * 64 * 64].clone()
-    sp.pair_xz = False
-    ref = sp.forward_zx(src, R, sp.G, out_name="gemm_fwd")[:R * ny * 64 * 64].clone()
-    assert normwise(got.cpu().numpy(), ref.cpu().numpy()) < 1e-14
-    X = src.reshape(R, ny, 32, 32)
-    G = sp.G["x"][:64, :32]
-    assert normwise(got.reshape(R, ny, 64, 64).cpu().numpy(), torch.einsum("ai,rpik,bk->rpab", G, X, G).cpu().numpy()) < 1e-14
     u2 = _rand((R * ny * 64 * 64 + 4096,), 91)
-    outs = []
-    for pair in (True, False):
-        sp.pair_xz = pair
+
+    def run(xz):
+        sp.forms = dataclasses.replace(planned, xz=xz)
+        fwd = sp.forward_zx(src, R, sp.G, out_name=xz + "_fwd")[:R * ny * 64 * 64].clone()
         out = torch.full((R, sp.N + 16), float("nan"), dtype=torch.float64, device="cuda")
         sp.backward_xz(u2, R, 0, ny, [(0, ny // 2, out, out.stride(0)), (ny // 2, ny, out[:, (ny // 2) * 1024:], out.stride(0))])
         assert torch.isnan(out[:, sp.N:]).all()
-        outs.append(out[:, :sp.N].clone())
-    assert normwise(outs[0].cpu().numpy(), outs[1].cpu().numpy()) < 1e-14
+        return fwd.cpu().numpy(), out[:, :sp.N].cpu().numpy()
+    ref_fwd, ref_inv = run("gemm")
+    G = sp.G["x"][:64, :32]
+    exact = torch.einsum("ai,rpik,bk->rpab", G, src.reshape(R, ny, 32, 32), G).cpu().numpy()
+    for xz in (("quad", "pair") if ny == 32 else ("pair",)):
+        fwd, inv = run(xz)
+        errs = normwise(fwd, ref_fwd), normwise(fwd.reshape(R, ny, 64, 64), exact), normwise(inv, ref_inv)
+        print("32 x 32 planes, ny = %d, %s: forward vs gemm %.2e, vs einsum %.2e, inverse vs gemm %.2e" % ((ny, xz) + errs))
+        assert max(errs) < 1e-14, (xz, errs)
+
+
+SPECTRAL_RECORD_GRIDS = [((64, 16, 64), "xz"), ((48, 16, 64), ""), ((64, 16, 32), ""), ((32, 16, 32), ""), ((32, 32, 32), ""), ((16, 16, 16), ""),
+                         ((80, 16, 16), "")]
+
+
+@pytest.mark.parametrize("dims,folded", SPECTRAL_RECORD_GRIDS)
+def test_spectral_product_runs_on_the_planners_record(hip, monkeypatch, dims, folded):
+    """SpectralProduct decides nothing: built on its own, with the process environment or with given options, its record is what
+    plan.stage_forms answers for the same arguments, y_mfma is read from it, and the folded matrices exist for exactly the axes whose
+    stages run on the radix-2 kernels (written out here: only the 64 x 64 (x, z) planes of 64 x 16 x 64, and none without the radix-2
+    switch).  Construction only."""
+    import os
+    from geobo_amd import plan
+    from geobo_amd.spectral import SpectralProduct
+    for name in plan.SWITCHES.values():
+        monkeypatch.delenv(name, raising=False)
+    off = plan.switches({"GEOBO_XZ_FOLD": "0"})
+    for opts, want, axes in ((None, plan.stage_forms(*dims, plan.switches(os.environ)), folded), (off, plan.stage_forms(*dims, off), "")):
+        sp = SpectralProduct(*dims, "cuda", opts=opts)
+        assert sp.forms == want
+        assert sp.y_mfma == (want.y == "mfma") == (dims[1] == 32)
+        assert sp.fused_xz == (want.xz in ("fold", "fused")) == ((dims[0], dims[2]) in ((64, 64), (48, 64), (64, 32)))
+        assert sorted(sp.F) == sorted(axes) == sorted(want.folded_axes())
+        assert hasattr(sp, "Fq") == (want.xz == "quad")
 
 
 @pytest.mark.parametrize("rows,C", [(1, 64), (3, 4096), (37, 192), (300, 4096)])

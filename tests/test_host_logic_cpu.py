@@ -266,10 +266,148 @@ def test_planner_and_kernel_wrappers_share_one_instance_table():
     from geobo_amd import hip, plan
     from geobo_amd.lattice_gram import LatticeGram
     assert hip.XZ2D_SHAPES is plan.XZ2D_SHAPES and hip.XZ2D_FOLD_N is plan.XZ2D_FOLD_N and hip.TOEPLITZ_NY is plan.TOEPLITZ_NY and hip.SPECTRAL_Y_NY is plan.SPECTRAL_Y_NY
+    from geobo_amd import spectral
+    assert hip.TOEPLITZ_ADD_NY is plan.TOEPLITZ_ADD_NY and hip.TOEPLITZ_Y2T_NY is plan.TOEPLITZ_Y2T_NY and hip.SPECTRAL_Y3T_NY is plan.SPECTRAL_Y3T_NY
+    assert hip.YMUL_SHAPES is plan.YMUL_SHAPES and spectral.INTEGER_BASIS_N is plan.INTEGER_BASIS_N and spectral.half_integer is plan.half_integer
     assert (hip.PAD_M, hip.PAD_N) == (plan.PAD_M, plan.PAD_N) == (256, 128)
     for dims in ((64, 64, 64), (64, 48, 64), (64, 32, 64), (32, 32, 32), (48, 64, 64), (128, 128, 128), (20, 16, 16)):
         assert LatticeGram.fast(*dims) == plan.lattice_gram_fast(*dims)
         assert LatticeGram.supported(*dims) == plan.lattice_gram_supported(*dims)
+
+
+# (grid, switch set to "0" | None) -> Forms fields in declaration order (xz, x_axis4, y, y_two_term, y3t, y2s, fold, ss, lattice_feed, plane_yx, gram_x,
+# gram_y_axis4, zx, z_mul, ymul_slabs).  A (grid, switch) pair of FORMS_SWITCHES that is not listed plans what the grid plans with nothing set.
+FORMS_SWITCHES = {"XZ_FOLD": "GEOBO_XZ_FOLD", "XZ_QUAD": "GEOBO_XZ_QUAD", "FUSED_XZ": "GEOBO_SPECTRAL_FUSED_XZ", "DENSE_Y": "GEOBO_SPECTRAL_DENSE_Y",
+                  "Y_MFMA": "GEOBO_Y_MFMA", "AXIS_MFMA": "GEOBO_AXIS_MFMA", "Z_FUSED": "GEOBO_Z_FUSED", "Z_MUL": "GEOBO_Z_MUL"}
+FORMS_TABLE = {
+    ((64, 64, 64), None): ('fold', 0, 'mfma', 'y2t', 0, 1, 1, 'fused', 1, 'fold', 'fold', 0, 1, 1, (64,)),
+    ((64, 64, 64), 'XZ_FOLD'): ('fused', 0, 'mfma', 'y2t', 0, 0, 0, 'stored', 0, 'fused', 'plain', 0, 0, 0, (64,)),
+    ((64, 64, 64), 'FUSED_XZ'): ('gemm', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'fold', 'fold', 0, 1, 1, (64,)),
+    ((64, 64, 64), 'DENSE_Y'): ('fold', 0, 'spectrum', 'y2t', 0, 0, 1, 'stored', 0, 'fold', 'fold', 0, 1, 1, (64,)),
+    ((64, 64, 64), 'Y_MFMA'): ('fold', 0, 'toeplitz', 'y2t', 0, 1, 1, 'fused', 1, 'fold', 'fold', 0, 1, 1, (64,)),
+    ((64, 64, 64), 'Z_FUSED'): ('fold', 0, 'mfma', 'y2t', 0, 1, 1, 'fused', 1, 'fold', 'fold', 0, 0, 0, (64,)),
+    ((64, 64, 64), 'Z_MUL'): ('fold', 0, 'mfma', 'y2t', 0, 1, 1, 'fused', 1, 'fold', 'fold', 0, 1, 0, (64,)),
+    ((64, 48, 64), None): ('fold', 0, 'mfma', 'y2t', 0, 1, 1, 'fused', 1, 'fused', 'fold', 0, 0, 0, ()),
+    ((64, 48, 64), 'XZ_FOLD'): ('fused', 0, 'mfma', 'y2t', 0, 0, 0, 'stored', 0, 'fused', 'plain', 0, 0, 0, ()),
+    ((64, 48, 64), 'FUSED_XZ'): ('gemm', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'fused', 'fold', 0, 0, 0, ()),
+    ((64, 48, 64), 'DENSE_Y'): ('fold', 0, 'spectrum', 'y2t', 0, 0, 1, 'stored', 0, 'fused', 'fold', 0, 0, 0, ()),
+    ((64, 48, 64), 'Y_MFMA'): ('fold', 0, 'toeplitz', 'y2t', 0, 1, 1, 'fused', 1, 'fused', 'fold', 0, 0, 0, ()),
+    ((64, 16, 64), None): ('fold', 0, 'toeplitz', 'separate', 0, 0, 1, 'fused', 1, 'gemm', 'fold', 0, 0, 0, ()),
+    ((64, 16, 64), 'XZ_FOLD'): ('fused', 0, 'toeplitz', 'separate', 0, 0, 0, 'stored', 0, 'gemm', 'plain', 0, 0, 0, ()),
+    ((64, 16, 64), 'FUSED_XZ'): ('gemm', 0, 'toeplitz', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold', 0, 0, 0, ()),
+    ((64, 16, 64), 'DENSE_Y'): ('fold', 0, 'spectrum', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold', 0, 0, 0, ()),
+    ((48, 64, 64), None): ('fused', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((48, 64, 64), 'XZ_FOLD'): ('fused', 0, 'mfma', 'y2t', 0, 0, 0, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, (64,)),
+    ((48, 64, 64), 'FUSED_XZ'): ('gemm', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((48, 64, 64), 'DENSE_Y'): ('fused', 0, 'spectrum', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((48, 64, 64), 'Y_MFMA'): ('fused', 0, 'toeplitz', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((64, 64, 32), None): ('fused', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'fold', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((64, 64, 32), 'XZ_FOLD'): ('fused', 0, 'mfma', 'y2t', 0, 0, 0, 'stored', 0, 'fused', 'gemm', 0, 0, 0, (64,)),
+    ((64, 64, 32), 'FUSED_XZ'): ('gemm', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'fold', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((64, 64, 32), 'DENSE_Y'): ('fused', 0, 'spectrum', 'y2t', 0, 0, 1, 'stored', 0, 'fold', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((64, 64, 32), 'Y_MFMA'): ('fused', 0, 'toeplitz', 'y2t', 0, 0, 1, 'stored', 0, 'fold', 'fold_lamdot', 0, 0, 0, (64,)),
+    ((32, 32, 32), None): ('quad', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 32, 32), 'XZ_FOLD'): ('pair', 0, 'mfma', 'y2t', 0, 0, 0, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, ()),
+    ((32, 32, 32), 'XZ_QUAD'): ('pair', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 32, 32), 'FUSED_XZ'): ('gemm', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 32, 32), 'DENSE_Y'): ('quad', 0, 'spectrum', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 32, 32), 'Y_MFMA'): ('quad', 0, 'toeplitz', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 16, 32), None): ('quad', 0, 'toeplitz', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 16, 32), 'XZ_FOLD'): ('pair', 0, 'toeplitz', 'separate', 0, 0, 0, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, ()),
+    ((32, 16, 32), 'XZ_QUAD'): ('pair', 0, 'toeplitz', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 16, 32), 'FUSED_XZ'): ('gemm', 0, 'toeplitz', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 16, 32), 'DENSE_Y'): ('quad', 0, 'spectrum', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 48, 32), None): ('quad', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 48, 32), 'XZ_FOLD'): ('pair', 0, 'mfma', 'y2t', 0, 0, 0, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, ()),
+    ((32, 48, 32), 'XZ_QUAD'): ('pair', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 48, 32), 'FUSED_XZ'): ('gemm', 0, 'mfma', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 48, 32), 'DENSE_Y'): ('quad', 0, 'spectrum', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((32, 48, 32), 'Y_MFMA'): ('quad', 0, 'toeplitz', 'y2t', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((16, 16, 16), None): ('gemm', 0, 'toeplitz', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((16, 16, 16), 'XZ_FOLD'): ('gemm', 0, 'toeplitz', 'separate', 0, 0, 0, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, ()),
+    ((16, 16, 16), 'DENSE_Y'): ('gemm', 0, 'spectrum', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((80, 16, 16), None): ('gemm', 1, 'toeplitz', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((80, 16, 16), 'XZ_FOLD'): ('gemm', 1, 'toeplitz', 'separate', 0, 0, 0, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, ()),
+    ((80, 16, 16), 'DENSE_Y'): ('gemm', 1, 'spectrum', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((80, 16, 16), 'AXIS_MFMA'): ('gemm', 0, 'toeplitz', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((96, 96, 96), None): ('gemm', 1, 'mfma', 'add', 1, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 1, 0, 0, ()),
+    ((96, 96, 96), 'XZ_FOLD'): ('gemm', 1, 'mfma', 'add', 1, 0, 0, 'stored', 0, 'gemm', 'gemm', 1, 0, 0, ()),
+    ((96, 96, 96), 'DENSE_Y'): ('gemm', 1, 'spectrum', 'add', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 1, 0, 0, ()),
+    ((96, 96, 96), 'Y_MFMA'): ('gemm', 1, 'toeplitz', 'add', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 1, 0, 0, ()),
+    ((96, 96, 96), 'AXIS_MFMA'): ('gemm', 0, 'mfma', 'add', 1, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((128, 128, 128), None): ('gemm', 1, 'mfma', 'add', 1, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 1, 0, 0, ()),
+    ((128, 128, 128), 'XZ_FOLD'): ('gemm', 1, 'mfma', 'add', 1, 0, 0, 'stored', 0, 'gemm', 'gemm', 1, 0, 0, ()),
+    ((128, 128, 128), 'DENSE_Y'): ('gemm', 1, 'spectrum', 'add', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 1, 0, 0, ()),
+    ((128, 128, 128), 'Y_MFMA'): ('gemm', 1, 'toeplitz', 'add', 0, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 1, 0, 0, ()),
+    ((128, 128, 128), 'AXIS_MFMA'): ('gemm', 0, 'mfma', 'add', 1, 0, 1, 'stored', 0, 'gemm', 'fold_lamdot', 0, 0, 0, ()),
+    ((144, 144, 144), None): ('gemm', 0, 'spectrum', 'separate', 0, 0, 1, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, ()),
+    ((144, 144, 144), 'XZ_FOLD'): ('gemm', 0, 'spectrum', 'separate', 0, 0, 0, 'stored', 0, 'gemm', 'gemm', 0, 0, 0, ()),
+    ((64, 128, 64), None): ('fold', 0, 'mfma', 'add', 1, 0, 1, 'fused', 1, 'gemm', 'fold', 1, 0, 0, ()),
+    ((64, 128, 64), 'XZ_FOLD'): ('fused', 0, 'mfma', 'add', 1, 0, 0, 'stored', 0, 'gemm', 'plain', 1, 0, 0, ()),
+    ((64, 128, 64), 'FUSED_XZ'): ('gemm', 0, 'mfma', 'add', 1, 0, 1, 'stored', 0, 'gemm', 'fold', 1, 0, 0, ()),
+    ((64, 128, 64), 'DENSE_Y'): ('fold', 0, 'spectrum', 'add', 0, 0, 1, 'stored', 0, 'gemm', 'fold', 1, 0, 0, ()),
+    ((64, 128, 64), 'Y_MFMA'): ('fold', 0, 'toeplitz', 'add', 0, 0, 1, 'fused', 1, 'gemm', 'fold', 1, 0, 0, ()),
+    ((64, 128, 64), 'AXIS_MFMA'): ('fold', 0, 'mfma', 'add', 1, 0, 1, 'fused', 1, 'gemm', 'fold', 0, 0, 0, ()),
+}
+
+
+def test_stage_forms_table():
+    """plan.stage_forms: the one record of which kernel form carries each stage, against a table generated ON THE PARENT of the change
+    that introduced it, from the objects that decided then: SpectralProduct(nx, ny, nz, "cpu", opts=plan.switches(env)) with hip.to_dev
+    patched to build host tensors gave fused_xz / quad_xz / pair_xz (in forward_zx's priority), x_mfma, dense_y / y_mfma, fold, fused_ss(),
+    lattice_feed and axis_mfma(ny); LatticeGram(sp, "cpu").zx_supported() gave zx (and with opts["z_mul"] z_mul); the ladders of
+    LatticeGram._lhat / gram_rows (plane_yx, gram_x), the membership tests of reduce_ss / y2s_tables (y_two_term, y3t, y2s) and
+    (2 ny, Ly) in hip.YMUL_SHAPES (ymul_slabs) were transcribed next to them."""
+    from geobo_amd.plan import Forms, plan_route, stage_forms, switches
+    grids = sorted({g for g, _ in FORMS_TABLE})
+    assert len(grids) == 14
+    for g in grids:
+        for name in (None,) + tuple(FORMS_SWITCHES):
+            env = {} if name is None else {FORMS_SWITCHES[name]: "0"}
+            want = Forms(*FORMS_TABLE.get((g, name), FORMS_TABLE[(g, None)]))
+            got = stage_forms(*g, switches(env))
+            assert got == want, (g, name, got, want)
+            r = plan_route(*g, env=env)
+            assert r.forms == want and dict(r.kernels)["xz"] == ("gemm+axis4" if (want.xz == "gemm" and want.x_axis4) else want.xz) and dict(r.kernels)["y"] == want.y
+            assert all(isinstance(v, (str, tuple)) or v is bool(v) for v in vars(got).values())
+    assert stage_forms(64, 64, 64) == Forms(*FORMS_TABLE[((64, 64, 64), None)])        # no options: every switch on
+    assert dict(plan_route(128, 128, 128).kernels)["xz"] == "gemm+axis4" and plan_route(128, 128, 128).forms.xz == "gemm"
+    assert stage_forms(64, 64, 64).folded_axes() == ("x", "y", "z") and stage_forms(64, 16, 64).folded_axes() == ("x", "z")
+    assert stage_forms(64, 64, 32).folded_axes() == ("x", "y") and stage_forms(32, 32, 32).folded_axes() == ()
+    assert stage_forms(64, 64, 64, switches({"GEOBO_SPECTRAL_FUSED_XZ": "0"})).folded_axes() == ("x", "y")   # (the Gram's x step and the (y, x) planes)
+
+
+def test_stage_forms_sweep_matches_the_parent_and_keeps_its_invariants():
+    """Every grid of extents 16 .. 160 in steps of 16 with nothing set and with every switch of plan.SWITCHES off singly (12 000 cases):
+    plan_route's kernels and family are what they were before the forms moved into stage_forms -- pinned by the SHA-256 of the sorted
+    list, produced on the parent commit by
+
+        ext = range(16, 161, 16)
+        envs = [()] + [((v, "0"),) for v in plan.SWITCHES.values()]
+        rows = sorted((nx, ny, nz, env, plan.plan_route(nx, ny, nz, env=dict(env)).kernels, plan.plan_route(nx, ny, nz, env=dict(env)).family)
+                      for nx, ny, nz in itertools.product(ext, ext, ext) for env in envs)
+        hashlib.sha256(repr(rows).encode()).hexdigest()
+
+    -- and every record satisfies the structural invariants of the forms."""
+    import hashlib
+    import itertools
+    from geobo_amd import plan
+    ext = range(16, 161, 16)
+    envs = [()] + [((v, "0"),) for v in plan.SWITCHES.values()]
+    rows = []
+    for nx, ny, nz in itertools.product(ext, ext, ext):
+        for env in envs:
+            r = plan.plan_route(nx, ny, nz, env=dict(env))
+            rows.append((nx, ny, nz, env, r.kernels, r.family))
+            f = r.forms
+            assert f == plan.stage_forms(nx, ny, nz, r.opts())
+            assert f.ss != "fused" or (f.xz == "fold" and f.y != "spectrum")
+            assert not f.lattice_feed or f.xz == "fold"
+            assert f.xz not in ("quad", "pair") or (nx, nz) == (32, 32)
+            assert not f.zx or (nx, ny, nz) == (64, 64, 64)
+            assert f.z_mul <= f.zx and f.y2s <= (f.ss == "fused") and f.y3t <= (f.y == "mfma")
+    assert len(rows) == 12000
+    assert hashlib.sha256(repr(sorted(rows)).encode()).hexdigest() == "57523179455e1db7fe4b4c78e54dad21c6b36c97354dbc91ae1c4aeda9d93309"
 
 
 def test_every_rank_plans_the_same_route():

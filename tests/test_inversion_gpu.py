@@ -1154,7 +1154,7 @@ def test_spectral_product_matches_lattice_contraction_on_non_cubic_grids(dims, k
     A = torch.zeros((rows, N + 16), dtype=torch.float64, device="cuda")[:, :N]
     A[:37] = (torch.rand((37, N), generator=g, dtype=torch.float64) * 2 - 1).cuda()
     sp = SpectralProduct(nx, ny, nz, "cuda")
-    assert sp.fused_xz == ((nx, nz) in ((48, 64), (64, 64))) and sp.dense_y == (ny in (16, 32, 48, 64, 80, 96, 112, 128))
+    assert (sp.forms.xz in ("fold", "fused")) == ((nx, nz) in ((48, 64), (64, 64))) and (sp.forms.y != "spectrum") == (ny in (16, 32, 48, 64, 80, 96, 112, 128))
     kid = hip.kernel_id(kern, cross)
     tabs = [hip.cov_table(kid, nx, ny, nz, 100.0, 90.0, 110.0, l1, l2, w, 1.3, "cuda")
             for l1, l2, w in ((210.0, 170.0, 0.7), (260.0, 240.0, 1.0), (150.0, 300.0, 0.4))]

@@ -9,7 +9,7 @@ from geobo_amd.spectral import SpectralProduct
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 R = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 sp = SpectralProduct(n, n, n, "cuda", rows_per_batch=R)
-assert not sp.fused_xz
+assert sp.forms.xz == "gemm"
 nx = ny = nz = n
 Px = Pz = 2 * n
 N = n ** 3
@@ -18,7 +18,7 @@ t1 = sp.buf("T1", R * ny * nx * Pz)
 t2 = sp.buf("T2", R * ny * Px * Pz)
 u1 = sp.buf("U1", R * ny * nx * Pz)
 out = torch.empty(R * N + 4096, dtype=torch.float64, device="cuda")
-fold = sp.fold
+fold = sp.forms.fold
 passes = {
     "z analysis  (FWD_Z)": (lambda: hip.axis_pass(fold, False, False, hip.pad_n(ny * nx), hip.pad_n(Pz), nz, src, nz, N, sp.G["z"], nz, 0, t1, Pz, ny * nx * Pz, ny * nx, Pz, R),
                             R * ny * nx * Pz * nz * 1.0, 8.0 * R * (N + ny * nx * Pz)),
@@ -29,7 +29,7 @@ passes = {
     "z synthesis (INV_Z)": (lambda: hip.axis_pass(fold, False, True, hip.pad_n(ny * nx), hip.pad_n(nz), Pz, u1, Pz, ny * nx * Pz, sp.GT["z"], Pz, 0, out, nz, N, ny * nx, nz, R),
                             R * ny * nx * nz * Pz * 1.0, 8.0 * R * (ny * nx * Pz + N)),
 }
-if sp.x_mfma:
+if sp.forms.x_axis4:
     # round 6: the x passes as radix-4 axis kernels on the half-integer basis (geobo_spectral_axis: n^2 / 2 multiply-adds per item and mode)
     passes["x analysis  (axis kernel)"] = (lambda: hip.spectral_axis(False, nx, Pz, Pz, Pz, nx * Pz, Px * Pz, R * ny, t1, t2),
                                            R * ny * Px * Pz * nx * 0.5, 8.0 * R * ny * (nx * Pz + Px * Pz))
