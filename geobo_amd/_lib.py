@@ -70,6 +70,7 @@ SIGNATURES = {
     "geobo_spectral_y_basis_doubles": (_i64, [_int]),
     "geobo_spectral_y_basis": (_int, [_int, _dp, _dp]),
     "geobo_spectral_y": (_int, [_int, _i64, _i64, _i64, _int, _dp, _dp, _dp, _dp, _dp, _int, _int, _dp, _dp]),
+    "geobo_spectral_y_lattice": (_int, [_int, _i64, _i64, _i64, _int, _dp, _dp, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _int, _int, _dp, _dp]),
     "geobo_spectral_y2s": (_int, [_int, _i64, _i64, _i64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "geobo_spectral_y3": (_int, [_int, _i64, _i64, _i64, _int, _dp, C.POINTER(_dp), C.POINTER(_dp), _int, _int, _int, _dp, _dp]),
     "geobo_spectral_y3t": (_int, [_int, _i64, _i64, _i64, _int, _dp, _dp, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp), _dp, _dp]),

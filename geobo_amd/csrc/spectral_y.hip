@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <stdint.h>
+#include <type_traits>
 #include "geobo_hip.h"
 
 namespace {
@@ -121,6 +122,17 @@ struct SYArgs {
   int y0, y1;
 };
 
+// Windowed rows (geobo_spectral_y_lattice; WIN instances of the kernel below): the input of row r is not a [NY][S] block of its own but a
+// window of a pool of planes shared between the rows -- plane y' at pool + row_off[r] + y' S for 0 < y' < NY - 1, the first and the
+// last plane at edge + r edge_row (+ S).  in[0] is the pool.  The rows are swept in the order `order` (nullptr: 0, 1, ..): neighbours
+// in the sweep whose windows overlap find their planes in cache.
+struct SYWinArgs : SYArgs {
+  const int64_t* row_off;   // [R] doubles
+  const double* edge;       // [R][edge_row], two planes S apart per row
+  int64_t edge_row;
+  const int32_t* order;     // [R] or nullptr
+};
+
 // one orbit's analysis butterfly: class sums C[rho], S[rho] -> (a_f, b_f), f = kappa, ny - kappa, ny/2 + kappa, ny/2 - kappa
 __device__ __forceinline__ void bfly_fwd(const double (&C)[4], const double (&S)[4], double (&a)[4], double (&b)[4]) {
   const double p0 = C[0] + C[2], p1 = C[0] - C[2], p2 = C[1] + C[3], p3 = C[1] - C[3];
@@ -129,11 +141,12 @@ __device__ __forceinline__ void bfly_fwd(const double (&C)[4], const double (&S)
   a[2] = p1 - q3; a[3] = p1 + q3; b[2] = q1 + p3; b[3] = p3 - q1;
 }
 
-template <int NY, int NIN, int NOUT, bool FULL>
-__global__ void __launch_bounds__(256, 1) spectral_y_kernel(SYArgs g) {
+template <int NY, int NIN, int NOUT, bool FULL, bool WIN>
+__global__ void __launch_bounds__(256, (WIN && NIN == 1 && NOUT == 1) ? 2 : 1) spectral_y_kernel(std::conditional_t<WIN, SYWinArgs, SYArgs> g) {
   using S = Shape<NY>;
   constexpr int NT = S::NT, MJ = S::MJ, KS = S::KS, NTAB = NIN == 2 ? 3 : NOUT;
   static_assert((NIN == 1 && NOUT >= 1 && NOUT <= 2) || (NIN == 2 && NOUT == 2), "forms");
+  static_assert(!WIN || NIN == 1, "windowed rows: one term");
   extern __shared__ __attribute__((aligned(16))) double frag[];           // [NF][64]
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 15, gq = lane >> 4;
@@ -183,8 +196,9 @@ __global__ void __launch_bounds__(256, 1) spectral_y_kernel(SYArgs g) {
     }
   };
 
-  auto body = [&](double (&x)[NIN][4 * KS], double (&xn)[NIN][4 * KS], int64_t row) {
-    if (row + rstep < g.R) load_row(xn, row + rstep);
+  // `prefetch` requests the next row of the sweep into the other register set
+  auto body = [&](double (&x)[NIN][4 * KS], int64_t row, auto&& prefetch) {
+    prefetch();
 #ifdef SY_ROW_BARRIER
     __builtin_amdgcn_s_barrier();
 #endif
@@ -288,23 +302,87 @@ __global__ void __launch_bounds__(256, 1) spectral_y_kernel(SYArgs g) {
   };
 
   double xa[NIN][4 * KS], xb[NIN][4 * KS];
-  load_row(xa, r);
-  while (true) {
-    body(xa, xb, r);
-    r += rstep;
-    if (r >= g.R) break;
-    body(xb, xa, r);
-    r += rstep;
-    if (r >= g.R) break;
+  if constexpr (!WIN) {
+    load_row(xa, r);
+    while (true) {
+      body(xa, r, [&] { if (r + rstep < g.R) load_row(xb, r + rstep); });
+      r += rstep;
+      if (r >= g.R) break;
+      body(xb, r, [&] { if (r + rstep < g.R) load_row(xa, r + rstep); });
+      r += rstep;
+      if (r >= g.R) break;
+    }
+  } else {
+    // Windowed rows.  Row group blockIdx.y sweeps the CONTIGUOUS positions [lo, hi) of the order (strided groups would interleave and
+    // take the shared planes of neighbouring positions apart); position i is row order[i], whose outputs stay at out[order[i]].
+    // A row's window is one descriptor at pool + row_off[row] (64-bit scalar arithmetic; the window itself stays under 2^31 bytes), its
+    // two boundary planes at edge + row edge_row.  Plane y' = 16 s + rho + 4 g: plane 0 is load (rho, s) = (0, 0) of lane group g = 0,
+    // plane NY - 1 load (3, KS - 1) of g = 3.  Those two loads take a per-lane ADDRESS -- the edge for that lane group, the window for the
+    // other three -- so that each stays one load into one register and no lane touches the pool plane in front of / behind the window's
+    // interior (which need not exist); the other fourteen keep the descriptor + scalar-offset form.
+    auto load_win = [&](double (&x)[NIN][4 * KS], int64_t row, int64_t off) {
+      const double* const pw = g.in[0] + off + m0;
+      const double* const pe = g.edge + row * g.edge_row + m0;
+      const rsrc_t rs = make_rsrc(pw, in_bytes);
+#pragma unroll
+      for (int rho = 0; rho < 4; ++rho)
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          double v;
+          if (rho == 0 && s == 0) {
+            const char* const a = gq == 0 ? reinterpret_cast<const char*>(pe) : reinterpret_cast<const char*>(pw) + (4 * gq) * S8;
+            v = *reinterpret_cast<const double*>(a + c * 8);
+          } else if (rho == 3 && s == KS - 1) {
+            const char* const a = gq == 3 ? reinterpret_cast<const char*>(pe + Sd) : reinterpret_cast<const char*>(pw) + (16 * s + rho + 4 * gq) * S8;
+            v = *reinterpret_cast<const double*>(a + c * 8);
+          } else {
+            v = ld_lane(rs, voff, (16 * s + rho) * S8);
+          }
+          x[0][rho * KS + s] = v;
+        }
+    };
+    const int64_t lo = g.R * blockIdx.y / gridDim.y, hi = g.R * (blockIdx.y + 1) / gridDim.y;
+    if (lo >= hi) return;
+    // the two index tables are read through the constant address space: nothing writes them during the launch, and a uniform load
+    // from there is a scalar load whatever the stores of the row loop may alias -- the row index and the window offset stay in scalar
+    // registers, the descriptors built from them are uniform (read as global memory they come back in vector registers and every
+    // buffer load of the row turns into a loop over the lanes' "different" descriptors)
+    typedef const __attribute__((address_space(4))) int32_t* const_i32;
+    typedef const __attribute__((address_space(4))) int64_t* const_i64;
+    const const_i32 order = (const_i32)g.order;
+    const const_i64 row_off = (const_i64)g.row_off;
+    auto row_at = [&](int64_t i) -> int64_t {
+      if (i >= hi) i = hi - 1;
+      return g.order ? (int64_t)order[i] : i;
+    };
+    // the sweep's indices run ahead of the loads in scalar registers: r1 = this row, r2 = the next (its window offset o2 already here
+    // when its loads are issued), r3 = the one after
+    int64_t pos = lo, r1 = row_at(lo), r2 = row_at(lo + 1), r3 = row_at(lo + 2);
+    int64_t o2 = row_off[r2];
+    load_win(xa, r1, row_off[r1]);
+    auto step = [&](double (&x)[NIN][4 * KS], double (&xn)[NIN][4 * KS]) {
+      const int64_t row = r1;
+      body(x, row, [&] {
+        if (pos + 1 < hi) load_win(xn, r2, o2);
+        r1 = r2; r2 = r3; o2 = row_off[r3]; r3 = row_at(pos + 3);
+      });
+      ++pos;
+    };
+    while (true) {
+      step(xa, xb);
+      if (pos >= hi) break;
+      step(xb, xa);
+      if (pos >= hi) break;
+    }
   }
 }
 
-template <int NY, int NIN, int NOUT, bool FULL>
-int launch_full(const SYArgs& g, hipStream_t st) {
+template <int NY, int NIN, int NOUT, bool FULL, bool WIN = false>
+int launch_full(const std::conditional_t<WIN, SYWinArgs, SYArgs>& g, hipStream_t st) {
   using S = Shape<NY>;
   constexpr size_t lds = (size_t)S::NF * 64 * sizeof(double);
   static_assert(lds <= 163840, "LDS");
-  auto kern = spectral_y_kernel<NY, NIN, NOUT, FULL>;
+  auto kern = spectral_y_kernel<NY, NIN, NOUT, FULL, WIN>;
   static std::atomic<uint64_t> attr_done{0};       // per-device "large-LDS attribute set" bits (include/geobo_hip.h, conventions)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
@@ -326,6 +404,11 @@ int launch_full(const SYArgs& g, hipStream_t st) {
 template <int NY, int NIN, int NOUT>
 int launch(const SYArgs& g, hipStream_t st) {
   return (g.y0 == 0 && g.y1 == NY) ? launch_full<NY, NIN, NOUT, true>(g, st) : launch_full<NY, NIN, NOUT, false>(g, st);
+}
+
+template <int NY, int NOUT>
+int launch_win(const SYWinArgs& g, hipStream_t st) {
+  return (g.y0 == 0 && g.y1 == NY) ? launch_full<NY, 1, NOUT, true, true>(g, st) : launch_full<NY, 1, NOUT, false, true>(g, st);
 }
 
 // ---- long y axes (ny = 80 .. 128; 128 = BASELINE config 5): FOUR waves share one tile of 16 modes ------------------------------------------
@@ -1032,6 +1115,26 @@ extern "C" int geobo_spectral_y(int ny, int64_t C, int64_t plane, int64_t R, int
     case 64: return nprop == 2 ? launch<64, 1, 2>(g, st) : launch<64, 1, 1>(g, st);
     case 48: return nprop == 2 ? launch<48, 1, 2>(g, st) : launch<48, 1, 1>(g, st);
     case 32: return nprop == 2 ? launch<32, 1, 2>(g, st) : launch<32, 1, 1>(g, st);
+    default: return GEOBO_E_UNSUPPORTED;
+  }
+}
+
+extern "C" int geobo_spectral_y_lattice(int ny, int64_t C, int64_t plane, int64_t R, int nprop, const double* pool, const int64_t* row_off,
+                                        const double* edge, int64_t edge_row, const int32_t* order, const double* tab0, const double* tab1,
+                                        double* out0, double* out1, int y0, int y1, const double* basis, void* stream) {
+  if (!pool || !row_off || !edge || !tab0 || !out0 || !basis || (nprop == 2 && (!tab1 || !out1))) return GEOBO_E_ARG;
+  if (nprop < 1 || nprop > 2 || R <= 0 || R >= (1ll << 31) || y0 < 0 || y1 > ny || y1 <= y0 || plane < C) return GEOBO_E_ARG;
+  if (C <= 0 || C % 16 || (int64_t)ny * plane * 8 >= (1ll << 31)) return GEOBO_E_ALIGN;
+  if ((plane & 1) || (edge_row & 1) || ((uintptr_t)pool & 15) || ((uintptr_t)edge & 15)) return GEOBO_E_ALIGN;
+  SYWinArgs g;
+  g.in[0] = pool; g.in[1] = pool; g.tab[0] = tab0; g.tab[1] = nprop == 2 ? tab1 : tab0; g.tab[2] = tab0;
+  g.out[0] = out0; g.out[1] = nprop == 2 ? out1 : out0; g.basis = basis; g.C = C; g.S = plane; g.R = R; g.y0 = y0; g.y1 = y1;
+  g.row_off = row_off; g.edge = edge; g.edge_row = edge_row; g.order = order;
+  hipStream_t st = (hipStream_t)stream;
+  switch (ny) {
+    case 64: return nprop == 2 ? launch_win<64, 2>(g, st) : launch_win<64, 1>(g, st);
+    case 48: return nprop == 2 ? launch_win<48, 2>(g, st) : launch_win<48, 1>(g, st);
+    case 32: return nprop == 2 ? launch_win<32, 2>(g, st) : launch_win<32, 1>(g, st);
     default: return GEOBO_E_UNSUPPORTED;
   }
 }

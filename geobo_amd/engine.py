@@ -646,7 +646,12 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                     continue
                 lams.append(gen)
                 outs.append(AK[s_ * self.Ms_pad:s_ * self.Ms_pad + self.Ms, jj * nc:(jj + 1) * nc])
-            fl, fv = sp.flops(self.Ms, len(lams), y1 - y0), sp.flops_valu(self.Ms, len(lams), y1 - y0)
+            # lattice survey, fp64 assembly: the y stage reads the rows as windows of the pool of distinct operator-plane spectra, built
+            # here once per operator and step (spectral.plane_pool) -- no forward transform per row
+            pooled = (isinstance(A, StreamedOperator) and A.lattice is not None and A.lattice.jy is not None and not self.f32
+                      and sp.pool_applies())
+            fl = sp.flops(self.Ms, len(lams), y1 - y0, fwd_planes=sp.pool_planes(self.Ms) if pooled else None)
+            fv = sp.flops_valu(self.Ms, len(lams), y1 - y0)
             if not self.f32 and not isinstance(A, StreamedOperator):
                 self._timed("spectral_product", fl, lambda: sp.product(A, self.Ms, lams, outs, y0, y1), valu=fv)
                 continue
@@ -657,9 +662,12 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                 Rb = sp.R
                 abuf = self._op_rows_buffer() if isinstance(A, StreamedOperator) else None
                 scr = [self._workspace2d("ak_rows64_%d" % jj, Rb, nc) for jj in range(len(lams))] if self.f32 else None
+                pool = sp.plane_pool(A.lattice, self.Ms, A.lattice.jy, A.lattice.jx) if pooled else None
                 for r0 in range(0, self.Ms, Rb):
                     R = min(Rb, self.Ms - r0)
-                    if abuf is not None and A.lattice is not None:
+                    if pool is not None:
+                        src = pool.rows(r0)                   # no rows and no transform of them: the y stage reads the pool
+                    elif abuf is not None and A.lattice is not None:
                         src = A.lattice.rows(r0)              # no rows at all: the forward transform reads the stencil table
                     else:
                         src = A.rows_into(abuf, r0, R) if abuf is not None else A[r0:r0 + R]

@@ -639,6 +639,26 @@ def spectral_y(ny, C, R, src, tabs, outs, y0=0, y1=None, plane=None, accumulate=
                                      1 if accumulate else 0, _p(spectral_y_basis(ny, src.device)), _stream()), "geobo_spectral_y3")
 
 
+def spectral_y_lattice(ny, C, R, pool, row_off, edge, edge_row, order, tabs, outs, y0=0, y1=None, plane=None):
+    """spectral_y on rows read as windows of a pool of (x, z)-spectrum planes (geobo_spectral_y_lattice; ny <= 64): row r = the planes at
+    pool + row_off[r] + y * plane between its two boundary planes edge[r * edge_row:] (+ plane), swept in the order `order` (int32
+    permutation or None).  One to three property blocks, two per sweep like spectral_y.  Bit-identical to spectral_y on the gather."""
+    lib = require_gpu()
+    y1 = ny if y1 is None else y1
+    n = len(tabs)
+    assert 1 <= n <= 3 and len(outs) == n
+    assert row_off.is_cuda and row_off.dtype == torch.int64 and row_off.is_contiguous() and row_off.numel() >= R
+    assert order is None or (order.is_cuda and order.dtype == torch.int32 and order.is_contiguous() and order.numel() == R)
+    basis = spectral_y_basis(ny, pool.device)
+    for j in range(0, n, 2):
+        two = j + 1 < n
+        _lib.check(lib.geobo_spectral_y_lattice(int(ny), int(C), int(C if plane is None else plane), int(R), 2 if two else 1, _p(_chk(pool, "pool")),
+                                                row_off.data_ptr(), _p(_chk(edge, "edge")), int(edge_row), order.data_ptr() if order is not None else None,
+                                                _p(_chk(tabs[j], "tab")), _p(_chk(tabs[j + 1], "tab")) if two else None,
+                                                _p(_chk(outs[j], "out")), _p(_chk(outs[j + 1], "out")) if two else None,
+                                                int(y0), int(y1), _p(basis), _stream()), "geobo_spectral_y_lattice")
+
+
 # SPECTRAL_Y3T_NY (plan.py): y extents of the two-term long-axis form (geobo_spectral_y3t)
 
 

@@ -35,7 +35,8 @@ class StreamedOperator:
             hip.a_sens(self.func, self.Bv, self.locd, nx, ny, nz, xed, yed, zed, self.mul, self.div, E2[:, k * plane:(k + 1) * plane], iy, iy + 1,
                        plan=self.plan, ws=self.lws, col_origin=iy * plane)
         self.edge = E2
-        self.lattice = LatticeRows(Q.view(-1), row_off, nqx * nz, E2)
+        # (host copies of the lattice indices: the pooled feed of the A K product builds its window tables from them, SpectralProduct.plane_pool)
+        self.lattice = LatticeRows(Q.view(-1), row_off, nqx * nz, E2, jy=self.plan["jy"].cpu().numpy(), jx=self.plan["jx"].cpu().numpy())
 
     def rows_into(self, buf, r0, R):
         """buf[:R, :N_pad] <- operator rows r0 .. r0+R-1 (voxel padding columns zero)."""

@@ -146,11 +146,65 @@ class LatticeRows:
     (hip.a_sens_lattice_stencil) at row_off[r] + y * q_plane, the two boundary planes come from `edge` ([rows][2][nx*nz]).
     forward_zx feeds the radix-2 forward kernel from this directly (geobo_xz2d_fold_lattice)."""
 
-    def __init__(self, Q, row_off, q_plane, edge, r0=0):
+    def __init__(self, Q, row_off, q_plane, edge, r0=0, jy=None, jx=None):
         self.Q, self.row_off, self.q_plane, self.edge, self.r0 = Q, row_off, int(q_plane), edge, int(r0)
+        self.jy, self.jx = jy, jx        # host copies of the survey plan's lattice indices per sensor (plane_pool)
 
     def rows(self, r0):
-        return LatticeRows(self.Q, self.row_off, self.q_plane, self.edge, self.r0 + r0)
+        return LatticeRows(self.Q, self.row_off, self.q_plane, self.edge, self.r0 + r0, self.jy, self.jx)
+
+
+# ---- the distinct-plane pool of a lattice operator (pure index arithmetic: tests/test_plane_pool_cpu.py) ---------------------------------
+# An interior plane y of row r sits at Q + row_off[r] + y q_plane with row_off[r] = ((ny-2-jy)(2nx-1) + (nx-1-jx)) nz: it depends on
+# (d = y - jy + ny - 2, jx) only.  The pool holds the (x, z)-spectrum of every such plane ONCE, laid out [jx' = nx-1-jx][d][Cp], so that
+# the ny planes of a row are contiguous: row r is the window at row_off'[r] = (jx' (2ny-3) + (ny-2-jy)) Cp.  (Planes 0 and ny - 1 of
+# the window are not the row's -- those are its own boundary slabs -- and for jy = ny - 1 / jy = 0 they lie in front of / behind
+# the block of jx': never read.)
+
+def pool_row_off(nx, ny, Cp, jy, jx):
+    """int64 window offsets row_off'[r] (doubles) into the interior pool [nx][2ny-3][Cp]."""
+    jy, jx = np.asarray(jy, dtype=np.int64), np.asarray(jx, dtype=np.int64)
+    return ((nx - 1 - jx) * (2 * ny - 3) + (ny - 2 - jy)) * int(Cp)
+
+
+def pool_layout(nx, ny, Ms, Cp):
+    """(interior planes, offset of the boundary pool, doubles between the boundary planes of consecutive rows, planes in all): the pool
+    buffer is the interior pool [nx][2ny-3][Cp] followed by [Ms][2][Cp], row r's planes 0 and ny - 1 -- its own, whatever its window."""
+    n_int = nx * (2 * ny - 3)
+    return n_int, n_int * int(Cp), 2 * int(Cp), n_int + 2 * int(Ms)
+
+
+def pool_plane_source(nx, ny, nz, p):
+    """Offset (doubles) into the stencil table Q[2ny-3][2nx-1][nz] of the nx*nz window that pool plane p = jx' (2ny-3) + d transforms:
+    what the pool's one forward launch reads with in_row = nz (rows = jx') and in_plane = (2nx-1) nz (planes = d)."""
+    jxp, d = np.divmod(np.asarray(p, dtype=np.int64), 2 * ny - 3)
+    return jxp * nz + d * ((2 * nx - 1) * nz)
+
+
+def pool_order(jy, jx):
+    """int32 permutation that sweeps a batch of rows by (jx, jy): rows of equal jx are consecutive with jy ascending -- neighbours are
+    the same window shifted by one plane."""
+    return np.lexsort((np.asarray(jy), np.asarray(jx))).astype(np.int32)
+
+
+def pool_distinct_planes(ny, jy, jx):
+    """Planes a batch of rows reads when every distinct one is read once: distinct interior (jx, d) + two boundary planes per row."""
+    jy, jx = np.asarray(jy, dtype=np.int64), np.asarray(jx, dtype=np.int64)
+    d = (ny - 2 - jy)[:, None] + np.arange(1, ny - 1, dtype=np.int64)[None, :]
+    return int(np.unique(jx[:, None] * (2 * ny - 3) + d).size) + 2 * int(jy.size)
+
+
+class PooledRows:
+    """Operator rows of a lattice survey as windows of the pool of distinct plane SPECTRA (SpectralProduct.plane_pool): the y stage reads
+    them in place (hip.spectral_y_lattice), no forward transform per row.  pool: [nx][2ny-3][Cp] then the boundary planes [Ms][2][Cp]
+    (`edge`, a view of the same buffer); row_off: int64 device offsets of the windows; jy / jx: host lattice indices (sweep order)."""
+
+    def __init__(self, pool, row_off, edge, jy, jx, r0=0, geo=None):
+        self.pool, self.row_off, self.edge, self.jy, self.jx, self.r0 = pool, row_off, edge, jy, jx, int(r0)
+        self.geo = geo if geo is not None else (jy.tobytes(), jx.tobytes())      # the survey's identity for the product's table cache
+
+    def rows(self, r0):
+        return PooledRows(self.pool, self.row_off, self.edge, self.jy, self.jx, self.r0 + r0, self.geo)
 
 
 class SpectralProduct:
@@ -202,7 +256,64 @@ class SpectralProduct:
         g = 128 // math.gcd(nx * ny, 128)
         self.R = max(g, rows_per_batch // g * g)
         self._bufs = {}
+        self._pool_tabs = {}         # index tables of the pooled feed per survey geometry (constants of the survey, unlike the pool)
         self.kernel_timer = None     # callable(name, algorithmic_bytes, fn) -> fn(): the engine's HIP-event bracket for single kernels
+
+    # lattice surveys: feed the A K y stage from the pool of distinct operator-plane spectra (plane_pool).  A plain attribute for A/B
+    # runs and tests; results are bit-identical either way
+    pooled_feed = True
+
+    def pool_applies(self):
+        """The pooled feed exists for one-term products on the in-kernel spectral y stage of ny <= 64 with the lattice forward kernel."""
+        return bool(self.pooled_feed and self.forms.lattice_feed and self.forms.y == "mfma" and self.ny in (32, 48, 64))
+
+    def pool_planes(self, Ms):
+        """Planes the pool of an Ms-sensor operator holds (= forward transforms of plane_pool)."""
+        return pool_layout(self.nx, self.ny, Ms, self.Cp)[3]
+
+    def plane_pool(self, lattice, Ms, jy, jx):
+        """(x, z)-spectra of every distinct plane of a lattice operator, each transformed once: the interior planes [nx][2ny-3][Cp] by ONE
+        forward launch over the stencil table itself (row jx' = the window nz doubles further on, plane d = one table plane further: the
+        windows overlap and are only read), the boundary slabs [Ms][2][Cp] by a second one.  Built per operator and step into a work
+        buffer of its own -- the table workspace is overwritten by the next operator, nothing here is kept across steps."""
+        assert self.pool_applies()
+        nx, ny, nz, Cp = self.nx, self.ny, self.nz, self.Cp
+        nd = 2 * ny - 3
+        n_int, edge_off, edge_row, planes = pool_layout(nx, ny, Ms, Cp)
+        buf = self.buf("Pool", planes * Cp)
+        hip.xz2d_fold(False, nx, nx, nd, lattice.Q, nz, lattice.q_plane, self.F["x"], self.F["z"], buf, nd * Cp, Cp)
+        e0 = lattice.edge[lattice.r0:]
+        edge = buf[edge_off:planes * Cp]
+        hip.xz2d_fold(False, nx, Ms, 2, e0, lattice.edge.stride(0), nx * nz, self.F["x"], self.F["z"], edge, edge_row, Cp)
+        # (jy / jx: the lattice indices of the rows the lattice view starts at, in the operator's own row order -- not assumed row-major)
+        jy, jx = np.ascontiguousarray(jy, dtype=np.int64)[:Ms], np.ascontiguousarray(jx, dtype=np.int64)[:Ms]
+        rows = PooledRows(buf, None, edge, jy, jx)
+        key = (rows.geo, Cp)
+        row_off = self._pool_tabs.get(key)
+        if row_off is None:
+            row_off = self._pool_tabs[key] = torch.from_numpy(pool_row_off(nx, ny, Cp, jy, jx)).to(self.device)
+        rows.row_off = row_off
+        return rows
+
+    def _pool_batch(self, A, r0, R):
+        """(device int32 sweep order, distinct planes) of the rows r0 .. r0 + R of a pooled operator (constants of the survey: kept)."""
+        a = A.r0 + r0
+        key = (A.geo, a, R)
+        hit = self._pool_tabs.get(key)
+        if hit is None:
+            jy, jx = A.jy[a:a + R], A.jx[a:a + R]
+            hit = self._pool_tabs[key] = (torch.from_numpy(pool_order(jy, jx)).to(self.device), pool_distinct_planes(self.ny, jy, jx))
+        return hit
+
+    def _ystage_pooled(self, A, r0, R, tabs, outs, y0, y1):
+        """The y stage of the rows r0 .. r0 + R of a pooled operator, in place from the pool.  Algorithmic bytes for the per-kernel
+        roofline: every distinct plane of the batch once + the output slabs."""
+        ny, C, Cp = self.ny, self.Px * self.Pz, self.Cp
+        order, distinct = self._pool_batch(A, r0, R)
+        a = A.r0 + r0
+        fn = lambda: hip.spectral_y_lattice(ny, C, R, A.pool, A.row_off[a:], A.edge[a * 2 * Cp:], 2 * Cp, order, tabs, outs, y0, y1, plane=Cp)
+        name = "kernel:toeplitz_y" if len(tabs) >= 2 else "kernel:toeplitz_y_single"
+        return self._launch(name, 8.0 * C * (distinct + R * len(tabs) * (y1 - y0)), R, self.y_stage_flop(1, len(tabs), y1 - y0), fn)
 
     # y per (x, z) mode inside one kernel (geobo_toeplitz_y), not by passes like x and z; there on the matrix pipe (round 6: geobo_spectral_y, same sums to rounding)
     dense_y = property(lambda self: self.forms.y != "spectrum")
@@ -325,8 +436,9 @@ class SpectralProduct:
                 hip.axis_pass(fold, False, True, hip.pad_n(slab * nx), hip.pad_n(nz), Pz, u1[(ya - ylo) * nx * Pz:], Pz, Ly * nx * Pz,
                               self.GT["z"], Pz, 0, out, nz, ldo, slab * nx, nz, R)
 
-    def flops(self, rows, nblocks, slab):
-        """Executed flop of product(): forward passes once, the rest per property block (compute extents)."""
+    def flops(self, rows, nblocks, slab, fwd_planes=None):
+        """Executed flop of product(): forward passes once, the rest per property block (compute extents).  fwd_planes: planes the
+        forward transform runs over when that is not rows * ny (the pooled feed transforms pool_planes(Ms) distinct ones)."""
         nx, ny, nz, Px, Py, Pz = self.nx, self.ny, self.nz, self.Px, self.Py, self.Pz
         pn = hip.pad_n
         fwd = 2.0 * (ny * nx * pn(Pz) * nz + ny * pn(Px) * pn(Pz) * nx)
@@ -348,6 +460,8 @@ class SpectralProduct:
         if not self.dense_y:
             fwd += 2.0 * pn(Py) * Px * Pz * ny
             bwd += 2.0 * pn(slab) * Px * Pz * Py
+        if fwd_planes is not None:
+            fwd *= float(fwd_planes) / (rows * ny)
         return rows * (fwd + nblocks * bwd + (self.y_stage_flop(1, nblocks, slab)[0] if self.dense_y else 0.0))
 
     def y_stage_flop(self, terms, nblocks, slab=None, shared=False):
@@ -398,7 +512,9 @@ class SpectralProduct:
         if slabs is None:
             slabs = [(y0, y1, outs)]
         N = self.N
-        if isinstance(A, LatticeRows):
+        if isinstance(A, PooledRows):
+            assert self.pool_applies() and self.dense_y
+        elif isinstance(A, LatticeRows):
             assert self.forms.lattice_feed
         else:
             assert A.stride(1) == 1 and A.stride(0) >= N and A.stride(0) % 2 == 0
@@ -431,14 +547,21 @@ class SpectralProduct:
         n_out = (yhi - ylo) * Cp
         for r0 in range(0, Ms, self.R):
             R = min(self.R, Ms - r0)
-            if isinstance(A, LatticeRows):
+            if isinstance(A, PooledRows):
+                t2 = None                                 # the rows' spectra are windows of the pool: nothing to transform
+            elif isinstance(A, LatticeRows):
                 t2 = self.forward_zx(A.rows(r0), R, self.G)
             else:
                 t2 = self.forward_zx(A[r0:], R, self.G, src_row_stride=A.stride(0))
             for j in range(0, len(gens), 3):              # up to three property blocks per read of the (x, z)-spectrum
                 js = list(range(j, min(j + 3, len(gens))))
                 u2 = [self.buf(("S", "S1", "S2")[i], R * n_out) for i in range(len(js))]
-                self._ystage(ny, C, R, t2, [gens[jj] for jj in js], u2, ylo, yhi, Cp)
+                if t2 is None:
+                    # (two blocks + one, each its own launch with its own bytes: what hip.spectral_y does inside one call)
+                    for i in range(0, len(js), 2):
+                        self._ystage_pooled(A, r0, R, [gens[jj] for jj in js[i:i + 2]], u2[i:i + 2], ylo, yhi)
+                else:
+                    self._ystage(ny, C, R, t2, [gens[jj] for jj in js], u2, ylo, yhi, Cp)
                 for i, jj in enumerate(js):
                     self.backward_xz(u2[i], R, ylo, yhi, [(ya, yb, o[jj][r0:], o[jj].stride(0)) for ya, yb, o in slabs])
 

@@ -423,6 +423,22 @@ int geobo_spectral_y(int ny, int64_t C, int64_t plane, int64_t R, int nprop, con
 int geobo_spectral_y2s(int ny, int64_t C, int64_t plane, int64_t R, const double* in_g, const double* in_m, const double* tab_d0,
                        const double* tab_x, const double* tab_d1, double* out0, double* out1, const double* basis, void* stream);
 
+/* geobo_spectral_y on rows that are WINDOWS of a pool of planes shared between them (the operator rows of a lattice survey, whose
+ * interior (x, z)-planes depend on the sensor's lattice offset only: every distinct plane is transformed once and kept once):
+ * plane y' of row r is the `plane` doubles at pool + row_off[r] + y' plane for 0 < y' < ny - 1; plane 0 is at edge + r edge_row and
+ * plane ny - 1 at edge + r edge_row + plane (the +-1e6 m boundary slabs of A_sens, each sensor's own).  Windows may overlap and
+ * repeat; of a window only its ny - 2 interior planes are read, so the planes in front of and behind them need not exist.
+ * row_off: R device int64 (doubles, any sign); a window spans ny plane 8 < 2^31 bytes, the pool itself may be larger.
+ * order: R device int32, a permutation of 0 .. R-1, or NULL for 0, 1, ..: the rows are swept in that order, every row group of the
+ * launch taking a contiguous run of it, so that neighbours whose windows overlap find their planes in cache (pool and edge are read
+ * with the default cache policy, the outputs stored non-temporally); outputs stay at out_j + r (y1 - y0) plane whatever the order.
+ * Operands, arithmetic and summation order per output are those of geobo_spectral_y on the gathered rows: bit-identical results.
+ * ny in {32, 48, 64}, nprop in {1, 2}; plane, edge_row even, pool and edge 16-byte aligned (GEOBO_E_ALIGN); otherwise the
+ * arguments and returns of geobo_spectral_y.  Stands for the same reference line: inversion.py:96 (A K, A never materialised). */
+int geobo_spectral_y_lattice(int ny, int64_t C, int64_t plane, int64_t R, int nprop, const double* pool, const int64_t* row_off,
+                             const double* edge, int64_t edge_row, const int32_t* order, const double* tab0, const double* tab1,
+                             double* out0, double* out1, int y0, int y1, const double* basis, void* stream);
+
 /* The same in-kernel spectral product for up to THREE property blocks per sweep (tabs / outs: HOST arrays of nprop device pointers) and
  * for the long y axes ny in {80, 96, 112, 128} (128: BASELINE config 5), the drop-in for geobo_toeplitz_y3 / geobo_toeplitz_y3_add
  * (accumulate != 0: outs[j] += the sums -- the second term of a two-term row).  There a lane can no longer hold a tile's spectrum and its

@@ -28,6 +28,8 @@ DRIVERS = {"posterior": ("run_posterior_once.py", "gemm_f64_kernel<4, 2, 2, 1", 
            "toeplitz2s": ("run_spectral_kernels_once.py toeplitz2s", "toeplitz_y2s_kernel", "pmc_toeplitz_y2s.json"),
            "spectral_y": ("run_spectral_kernels_once.py spectral_y", "spectral_y_kernel<64, 1, 2", "pmc_spectral_y.json"),
            "spectral_y1": ("run_spectral_kernels_once.py spectral_y1", "spectral_y_kernel<64, 1, 1", "pmc_spectral_y1.json"),
+           "spectral_y_pool": ("run_spectral_kernels_once.py spectral_y_pool", "spectral_y_kernel<64, 1, 2", "pmc_spectral_y_pool.json"),
+           "spectral_y1_pool": ("run_spectral_kernels_once.py spectral_y1_pool", "spectral_y_kernel<64, 1, 1", "pmc_spectral_y1_pool.json"),
            "spectral_y2s": ("run_spectral_kernels_once.py spectral_y2s", "spectral_y_kernel<64, 2, 2", "pmc_spectral_y2s.json"),
            "spectral_y128": ("run_spectral_kernels_once.py spectral_y128", "spectral_y_pipe_kernel<128, 1, 3", "pmc_spectral_y128.json"),
            "spectral_y128_1": ("run_spectral_kernels_once.py spectral_y128_1", "spectral_y_pipe_kernel<128, 1, 1", "pmc_spectral_y128_1.json"),
@@ -68,6 +70,9 @@ def main():
         sc = script.split()
         cmd = ["rocprofv3", "--pmc", *grp, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.join(HERE, sc[0]), *sc[1:]]
         r = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), capture_output=True, text=True)
+        if r.returncode != 0:             # a failed pass ends the collection: nothing more is started on the device
+            sys.stderr.write(r.stdout[-2000:] + r.stderr[-2000:])
+            sys.exit("pmc pass %s of %s ended with status %d" % (",".join(grp), script, r.returncode))
         text = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else text
         ndisp = {}
         for f in glob.glob(os.path.join(d, "*", "*counter_collection.csv")):

@@ -61,6 +61,23 @@ if which in ("all", "spectral_y", "spectral_y1", "spectral_y2s"):
     if which in ("all", "spectral_y2s"):
         timed("spectral_y2s", R * C * (4.0 * n * n + 28.0 * n), R * n * C * 8.0 * 4, lambda: hip.spectral_y2s(n, C, R, src_g, src_m, t3[0], t3[1], t3[2], outs))
     del src_g, src_m, t3, outs
+if which in ("spectral_y_pool", "spectral_y1_pool"):
+    # the A K y stage fed from the pool of distinct operator-plane spectra (geobo_spectral_y_lattice) at the 64^3 batch shape: 256 rows =
+    # 4 jy x 64 jx of a row-major lattice survey, swept by (jx, jy); algorithmic bytes = every distinct plane of the batch once + outputs
+    import numpy as np
+    from geobo_amd.spectral import pool_distinct_planes, pool_layout, pool_order, pool_row_off
+    C = P * P
+    jy, jx = np.repeat(np.arange(30, 34), n), np.tile(np.arange(n), 4)
+    n_int, edge_off, edge_row, planes = pool_layout(n, n, R, C)
+    buf = rnd(planes * C)
+    row_off = torch.from_numpy(pool_row_off(n, n, C, jy, jx)).to(dev)
+    order = torch.from_numpy(pool_order(jy, jx)).to(dev)
+    nb = 2 if which == "spectral_y_pool" else 1
+    tabs = [rnd(n * C) for _ in range(nb)]
+    outs = [torch.empty(R * n * C, dtype=torch.float64, device=dev) for _ in range(nb)]
+    timed(which, R * C * ((1.0 + nb) * n * n + (4.0 + 7.0 * nb) * n), 8.0 * C * (pool_distinct_planes(n, jy, jx) + R * nb * n),
+          lambda: hip.spectral_y_lattice(n, C, R, buf, row_off, buf[edge_off:], edge_row, order, tabs, outs))
+    del buf, tabs, outs
 if which in ("spectral_y128", "spectral_y128_1", "spectral_y3t128"):
     # the long-axis form (four waves per 16-mode tile) at the 128^3 batch shape: 32 rows of 128 planes x 65536 modes
     ny_, Rb, C = 128, 32, 4 * 128 * 128
