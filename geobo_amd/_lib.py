@@ -93,6 +93,9 @@ SIGNATURES = {
     "geobo_spectral_mix": (_int, [_int, _i64, _int, _int, _int, _dp, _f64, _dp, _dp, _dp]),
     "geobo_set_gram": (_int, [_i64, _int, _dp, _i64, _dp, _i64, _i64, _int, _dp, _dp]),
     "geobo_set_logdet": (_int, [_i64, _int, _dp, _dp, _i64, _f64, _dp, _dp, _i64, _dp, _dp, _dp]),
+    "geobo_kinv_diag_ws_bytes": (_sz, [_i64]),
+    "geobo_kinv_diag": (_int, [_i64, _dp, _i64, _dp, _dp, _dp, _dp, _sz, _dp]),
+    "geobo_set_loo": (_int, [_i64, _int, _dp, _dp, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _dp]),
     "geobo_trmv_stats": (_int, [_i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _dp]),
     "geobo_mfma_f64_peak": (_int, [_int, _int, _dp, _dp]),
     "geobo_mfma_mix": (_int, [_int, _int, _int, _int, _dp, _dp]),

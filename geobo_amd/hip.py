@@ -864,6 +864,52 @@ def set_logdet(G, Kpp, sigma2, idx, n_obs, observed=None, out=None, status=None)
     return out, status
 
 
+def kinv_diag_ws_doubles(m):
+    return max(_lib.load().geobo_kinv_diag_ws_bytes(int(m)) // 8, 1)
+
+
+def kinv_diag(Linv, u, ws=None, d=None, alpha=None):
+    """d[c] = sum_r Linv[r, c]^2 (the diagonal of K^-1 = Linv^T Linv) and alpha = Linv^T u, from the lower triangle of Linv alone
+    (m x m, m % 256 == 0, even leading dimension); the strict upper triangle is never read.  Returns (d, alpha)."""
+    lib = require_gpu()
+    m = Linv.shape[0]
+    ldl = _rowmajor(Linv, "Linv")
+    u = _chk(u, "u")
+    assert Linv.shape[1] == m and u.is_contiguous() and u.numel() >= m
+    if d is None:
+        d = torch.empty(m, dtype=F64, device=Linv.device)
+    if alpha is None:
+        alpha = torch.empty(m, dtype=F64, device=Linv.device)
+    assert d.is_contiguous() and alpha.is_contiguous() and d.numel() >= m and alpha.numel() >= m
+    nbytes = lib.geobo_kinv_diag_ws_bytes(m)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = torch.empty(max(nbytes // 8, 1), dtype=F64, device=Linv.device)
+    _lib.check(lib.geobo_kinv_diag(m, _p(Linv), ldl, _p(u), _p(_chk(d, "d")), _p(_chk(alpha, "alpha")), _p(_chk(ws, "ws")), nbytes,
+                                   _stream()), "geobo_kinv_diag")
+    return d, alpha
+
+
+def set_loo(G, idx, alpha, n=None):
+    """Leave-fold-out prediction of the C folds idx ((C, k) int32 rows, entries outside [0, n) are padding) from G[c] = [K^-1]_BB
+    (set_gram) and alpha = K^-1 y: returns (out (2, C) = [log p(y_B | y_-B), white.white], resid, var, white (C, k each, NaN at
+    padding), status (C,) int32 = 0 or 1 + failing pivot (NaN in everything of that fold))."""
+    lib = require_gpu()
+    if not (isinstance(idx, torch.Tensor) and idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 2 and idx.is_contiguous()):
+        raise TypeError("idx must be a contiguous (C, k) CUDA int32 tensor")
+    C_, k = idx.shape
+    _chk(G, "G")
+    alpha = _chk(alpha, "alpha")
+    n = alpha.numel() if n is None else int(n)
+    assert G.is_contiguous() and tuple(G.shape) == (C_, k, k) and alpha.is_contiguous() and alpha.numel() >= n
+    dev = G.device
+    out = torch.empty((2, C_), dtype=F64, device=dev)
+    resid, var, white = (torch.empty((C_, k), dtype=F64, device=dev) for _ in range(3))
+    status = torch.empty(C_, dtype=torch.int32, device=dev)
+    _lib.check(lib.geobo_set_loo(C_, k, _p(G), _p(idx), _p(alpha), n, _p(out), _p(resid), _p(var), _p(white), _p(status), _stream()),
+               "geobo_set_loo")
+    return out, resid, var, white, status
+
+
 def mfma_f64_peak(blocks=1024, iters=20000):
     """Time the v_mfma_f64_16x16x4_f64 issue rate; returns TFLOP/s (4 waves/WG x 16 MFMA x 2048 flop per iter)."""
     lib = require_gpu()

@@ -459,6 +459,112 @@ class Inversion:
         if getattr(self, "_step_params", None) != want or eng.last is None or tuple(eng.last["props"]) != (0, 1, 2):
             self._run(self.gp_amp, self.gp_length, None, False, False)
 
+    # ---- cross-validation ----------------------------------------------------------------------------------
+    CV_FOLDS = ("loo", "holes", "patches")
+
+    def _cv_folds(self, folds, cell):
+        """The fold list of a fold kind ("loo", "holes", "patches"), or the caller's own list of index arrays."""
+        from . import crossval
+        s = self.settings
+        Ms = self.gravfield.size
+        if not isinstance(folds, str):
+            return folds
+        if folds == "loo":
+            return crossval.loo_folds(self.Fs3.size)
+        if folds == "holes":
+            return crossval.hole_folds(self._sel, s.zNcube, Ms)
+        cell = 2.0 * s.xvoxsize if cell is None else float(cell)
+        return crossval.patch_folds(np.asarray(self.sensor_locations, dtype=float)[:, :2], cell, Ms, sel=self._sel, nz=s.zNcube)
+
+    def _check_cv_folds(self, folds):
+        if isinstance(folds, str) and folds not in self.CV_FOLDS:
+            raise ValueError("folds must be one of %s or a list of index arrays, got %r" % (self.CV_FOLDS, folds))
+
+    def cross_validate(self, folds="loo", cell=None, write=False):
+        """Leave-fold-out cross-validation of the fit, after cubing(): every data row is predicted from the rows outside its fold,
+        from the factor the step left on the device (no refactorisation; one step without mean and variance when the hyper-parameters
+        changed since).  folds: "loo" (one row each), "holes" (the drill rows of one voxel column together, sensors alone), "patches"
+        (sensors in square cells of side `cell` metres, default two x-voxels, binned by their coordinates; drill rows by hole) or a
+        list of disjoint index arrays into the data vector [grav | magn | drill], at most 128 rows each.  `cell` matters for "patches"
+        alone and is ignored otherwise.
+        Returns a dict: `grav`, `magn`, `drill` with `observed`, `predicted`, `residual`, `std`, `fit_residual` in the data units of
+        that type (deviations from the data mean, as cubing()'s cubes), `z` = residual / std and `fold` (-1: row in no fold);
+        `fit_residual`: the in-sample misfit y - A3 mu = D alpha of every row, normalised units; `folds`: `logp` (log predictive
+        density of the fold), `mahalanobis`, `size`, `status` (0, or 1 + the pivot at which the fold's block failed); `summary`:
+        `logp` (total) and per data type `mean_z2` and `mean_mahalanobis` (mean of mahalanobis / size over the folds that lie in that
+        type), both about 1 for a calibrated model.  write=True: crossval_grav.csv, crossval_magn.csv, crossval_drill.csv in outpath."""
+        self._check_cv_folds(folds)
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("cross_validate() predicts the survey of cubing(): call cubing() first")
+        eng = self.engine
+        want = _hyper_key(self.gp_amp, create_cov_lengths(np.array(self.gp_length, dtype=float)), self.coeffm)
+        if getattr(self, "_step_params", None) != want or eng.last is None:
+            self._run(self.gp_amp, self.gp_length, None, False, False)
+        r = {k: v.cpu().numpy() for k, v in eng.cross_validate(self._cv_folds(folds, cell)).items()}
+        ng, nm, Mu = self.gravfield.size, self.magfield.size, self.Fs3.size
+        sig = np.concatenate([np.full(ng, float(self.gp_sigma[0])), np.full(nm, float(self.gp_sigma[1])),
+                              np.full(Mu - ng - nm, float(self.gp_sigma[2]))])
+        fit = sig ** 2 * r["alpha"]
+        out = dict(fit_residual=fit, folds={k: r[k] for k in ("logp", "mahalanobis", "size", "status")})
+        summary = dict(logp=float(np.sum(r["logp"])))
+        # the type of a fold: that of all its rows (a fold over several types counts for none)
+        first = np.full(r["size"].size, Mu, dtype=np.int64)
+        lastr = np.full(r["size"].size, -1, dtype=np.int64)
+        rows = np.flatnonzero(r["fold_of_row"] >= 0)
+        np.minimum.at(first, r["fold_of_row"][rows], rows)
+        np.maximum.at(lastr, r["fold_of_row"][rows], rows)
+        with np.errstate(all="ignore"):
+            for i, (name, a, b) in enumerate((("grav", 0, ng), ("magn", ng, ng + nm), ("drill", ng + nm, Mu))):
+                sc = self._cube_scale[i]
+                obs, res, std = self.Fs3[a:b] * sc, r["resid"][a:b] * sc, np.sqrt(r["var"][a:b]) * sc
+                out[name] = dict(observed=obs, predicted=obs - res, residual=res, std=std, z=res / std, fold=r["fold_of_row"][a:b],
+                                 fit_residual=fit[a:b] * sc)
+                inside = (first >= a) & (lastr < b) & (lastr >= 0)
+                z = out[name]["z"]
+                summary[name] = dict(mean_z2=float(np.nanmean(z ** 2)) if np.isfinite(z).any() else float("nan"),
+                                     mean_mahalanobis=float(np.mean(r["mahalanobis"][inside] / r["size"][inside])) if inside.any() else float("nan"))
+        out["summary"] = summary
+        if write:
+            self._write_crossval(out)
+        return out
+
+    def _write_crossval(self, out):
+        """crossval_<type>.csv in outpath: sensor positions as passed to cubing() (voxel centres and DEPTH for the drill rows)."""
+        import os
+
+        import pandas as pd
+        s = self.settings
+        loc = np.asarray(self.sensor_locations, dtype=float)
+        for name in ("grav", "magn", "drill"):
+            o = out[name]
+            cols = dict(OBSERVED=o["observed"], PREDICTED=o["predicted"], STD=o["std"], Z=o["z"], FOLD=o["fold"])
+            if name == "drill":
+                pos = dict(EASTING=self.voxelpos[0][self._sel], NORTHING=self.voxelpos[1][self._sel], DEPTH=self.voxelpos[2][self._sel])
+            else:
+                pos = dict(EASTING=loc[:, 0], NORTHING=loc[:, 1])
+            pd.DataFrame({**pos, **cols}).to_csv(os.path.join(s.outpath, "crossval_%s.csv" % name), index=False)
+
+    def calc_cv(self, params, folds="holes"):
+        """Minus the total log predictive density of the folds (see cross_validate) for hyper-parameters (amplitude, lengthscale, 3
+        correlation coefficients): calc_logl's signature and parameter handling, an objective for the derivative-free optimisers.  One
+        step without mean and variance, then the folds; inf where the factorisation of the step fails (as calc_logl: with matern32 this
+        5-parameter form puts two equal lengths into the cross term, so it is inf there for every params) and where a fold's block
+        does not factorise.  Errors of the folds themselves (a hole of more than 128 voxels, a multi-rank engine) are raised.
+        "patches" has no `cell` here: two x-voxels."""
+        self._check_cv_folds(folds)
+        s = self.settings
+        gp_amp = params[0]
+        gp_length = params[1] * np.asarray([s.xvoxsize, s.xvoxsize, s.xvoxsize])
+        coeffm = params[2:]
+        from . import crossval
+        table = crossval.fold_table(self._cv_folds(folds, None), self.Fs3.size)
+        try:
+            self._run(gp_amp, gp_length, coeffm, False, False)
+        except (CholeskyError, FactorisationTimeout):
+            return np.inf
+        total = float(self.engine.cross_validate(table)["logp"].sum())
+        return -total if np.isfinite(total) else np.inf
+
     def hole_statistics(self, paths=None):
         """Posterior statistics of the drill property along holes, after cubing():
             info_gain = 1/2 log det(I + Sigma_PP / sigma_d^2)  (nats, scale-free),  path_std = sqrt(1^T Sigma_PP 1),  sum_var = trace Sigma_PP

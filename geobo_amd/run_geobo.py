@@ -35,7 +35,12 @@ def run(settings, method="auto", bayesopt=True, write=True):
         voxelsize = (s.xvoxsize, s.yvoxsize, s.zvoxsize)
         for c, n in zip(cubes, names):
             dataio.create_vtkcube(c, origin, voxelsize, fname=os.path.join(s.outpath, n + ".vtk"))
+    cv = getattr(s, "cross_validate", None)               # optional YAML key cross_validate: loo | holes | patches
+    if cv:
+        cv_result = inv.cross_validate(folds=str(cv), write=write)
     out = dict(zip(names, cubes), inversion=inv, drillcoord=drillcoord, inputs=(gravfield, magfield, drillfield, sensor_locations, drilldata0))
+    if cv:
+        out["cross_validation"] = cv_result
     nsamp = int(getattr(s, "posterior_samples", 0) or 0)     # optional YAML keys posterior_samples (default 0) and sample_seed
     if nsamp > 0:
         samples = inv.sample_posterior(nsamp, seed=int(getattr(s, "sample_seed", 0) or 0))

@@ -42,7 +42,9 @@ extern "C" {
  * Also additive since 212, version unchanged: the prior sampler of sampling.hip (geobo_philox_fill, geobo_torus_table,
  * geobo_fft_lines, geobo_fft_axis, geobo_sample_factor, geobo_sample_factor_ws_bytes, geobo_sample_zpass, geobo_spectral_mix).
  * Also additive since 212, version unchanged: the per-set posterior statistics of information.hip (geobo_set_gram,
- * geobo_set_logdet). */
+ * geobo_set_logdet).
+ * Also additive since 212, version unchanged: the cross-validation kernels of crossval.hip (geobo_kinv_diag,
+ * geobo_kinv_diag_ws_bytes, geobo_set_loo). */
 
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
@@ -626,6 +628,30 @@ int geobo_set_gram(int64_t C, int k, const int32_t* idx, int64_t R, const double
  * sigma2 not positive (GEOBO_E_ARG). */
 int geobo_set_logdet(int64_t C, int k, const double* G, const double* Kpp, int64_t kpp_stride, double sigma2, const int32_t* idx,
                      const uint8_t* observed, int64_t n_obs, double* out, int* status, void* stream);
+
+/* ---- cross-validation (crossval.hip) ----------------------------------------------------------------------
+ * d[c] = sum_{r >= c} Linv[r,c]^2 (the diagonal of K^-1 = Linv^T Linv) and alpha[c] = sum_{r >= c} Linv[r,c] u[r] (K^-1 y for
+ * u = Linv y), c < m, in one pass over the lower triangle of Linv (m x m row-major, leading dimension ldl).  The strict upper
+ * triangle is never read.  Tiles of 256 columns x slices of 128 rows from the tile's diagonal down, rows added in ascending order;
+ * one slot of 2 x 256 partial sums per (tile, slice) in ws, added per tile in slice order by a finish pass: no atomics, bitwise
+ * reproducible, independent of what ws held.  geobo_kinv_diag_ws_bytes(m) = nb (nb + 1) * 2 * 256 * 8 with nb = m / 256, and 0
+ * for an invalid m.  m % 256 == 0, m <= 2^20, ldl >= m and even, Linv and ws 16-byte aligned.  Every argument check comes before
+ * any device access (GEOBO_E_ARG). */
+size_t geobo_kinv_diag_ws_bytes(int64_t m);
+int geobo_kinv_diag(int64_t m, const double* Linv, int64_t ldl, const double* u, double* d, double* alpha, void* ws, size_t ws_bytes,
+                    void* stream);
+
+/* Leave-fold-out prediction for C folds of k <= 128 rows: G (C x k x k) holds the blocks [K^-1]_BB (geobo_set_gram over the columns
+ * idx of Linv), idx (C x k int32) the rows of each fold, alpha (n doubles) K^-1 y; an entry of idx outside [0, n) is padding (unit
+ * row and column).  Per fold, over its live entries: Cholesky G = Lg Lg^T in LDS, white = Lg^-1 alpha_B, resid = Lg^-T white
+ * (= y_B - E[y_B | y_-B]), var_a = (G^-1)_aa (the predictive variance of row a given every row outside the fold),
+ *   out[c] = -1/2 white^T white + sum log diag Lg - (k_live / 2) log 2 pi  (= log p(y_B | y_-B)),   out[C + c] = white^T white,
+ *   resid, var, white: C x k, NaN at padding entries,
+ *   status[c] = 0, or 1 + the first non-positive pivot, with NaN in everything of that fold (the other folds are unaffected).
+ * One workgroup per fold, fixed-order sums.  Checks before any device access: NULL pointers, C < 0, k < 1, k > 128, n < 0
+ * (GEOBO_E_ARG).  C == 0 is a no-op. */
+int geobo_set_loo(int64_t C, int k, const double* G, const int32_t* idx, const double* alpha, int64_t n, double* out, double* resid,
+                  double* var, double* white, int* status, void* stream);
 
 #ifdef __cplusplus
 }
