@@ -910,6 +910,40 @@ def set_loo(G, idx, alpha, n=None):
     return out, resid, var, white, status
 
 
+def block_cov_ws_doubles(R, grid, box):
+    """Workspace of block_cov for R rows, grid (ny, nx, nz) and box (by, bx, bz), in doubles."""
+    nbytes = _lib.load().geobo_block_cov_ws_bytes(int(R), *(int(v) for v in grid), *(int(v) for v in box))
+    if nbytes == 0:
+        raise ValueError("block_cov: invalid rows %r, grid %r or box %r" % (R, tuple(grid), tuple(box)))
+    return nbytes // 8
+
+
+def block_cov(V, R, grid, box, C6, accumulate=False, ws=None):
+    """C6[B] = (accumulate ? C6[B] : 0) + sum_{r < R} s_a[r, B] s_b[r, B] in the order (00, 01, 02, 11, 12, 22), s_a[r, B] the sum of
+    V[a][r] over the voxels of block B (boxes of `box` = (by, bx, bz) voxels tiling `grid` = (ny, nx, nz) from the origin, partial at
+    the far edges; block index (jy nbx + jx) nbz + jz).  V: three 2-D fp64 tiles of one leading dimension, columns in voxel order
+    (iy, ix, iz); C6: (nblocks, 6) fp64."""
+    lib = require_gpu()
+    ldv = _rowmajor(V[0], "V")
+    R = int(R)
+    grid, box = tuple(int(v) for v in grid), tuple(int(v) for v in box)
+    N = grid[0] * grid[1] * grid[2]
+    for t in V:
+        if _rowmajor(t, "V") != ldv or t.shape[0] < R or t.shape[1] < N:
+            raise ValueError("the three tiles must share a leading dimension and hold R x N elements")
+    nblocks = 1
+    for n, b in zip(grid, box):
+        nblocks *= (n + max(b, 1) - 1) // max(b, 1)
+    _chk(C6, "C6")
+    assert C6.is_contiguous() and tuple(C6.shape) == (nblocks, 6)
+    need = block_cov_ws_doubles(R, grid, box)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=F64, device=C6.device)
+    _lib.check(lib.geobo_block_cov(R, _p(V[0]), _p(V[1]), _p(V[2]), ldv, *grid, *box, 1 if accumulate else 0, _p(C6), _p(_chk(ws, "ws")),
+                                   ws.numel() * 8, _stream()), "geobo_block_cov")
+    return C6
+
+
 def mfma_f64_peak(blocks=1024, iters=20000):
     """Time the v_mfma_f64_16x16x4_f64 issue rate; returns TFLOP/s (4 waves/WG x 16 MFMA x 2048 flop per iter)."""
     lib = require_gpu()

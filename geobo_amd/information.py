@@ -15,6 +15,8 @@ Two sources of V_d tiles, by the route the step took:
             the drill term only in the rows behind the sensor rows (L^-1 is lower triangular), as in _drill_rows_ss.
   generic   every other one-rank fp64 step: L^-1 (A K)[:, drill block] by MFMA GEMMs when A K is whole, otherwise rows of Z by
             GEMMs against the operator rows (as condition() forms A3^T W) and K through the prior sampler's exact circulant product.
+Both generators yield the tiles of any list of property blocks in lockstep (the drill block alone by default): the block-support
+statistics of blocksupport.py sweep all three, with one forward transform of Z per operator term.
 """
 import numpy as np
 import torch
@@ -50,9 +52,11 @@ class SetStatisticsMixin:
             hit = self._set_smp = (key, smp)
         return hit[1]
 
-    def _vd_spectral(self, step, prior, Linv, A_g, A_m):
-        """Tiles (V, n) of 128 rows of V_d on the transposed route, voxel order (iy, ix, iz): the generators of the step whose factor
-        Linv is, the drill block's from `prior`."""
+    def _v_spectral(self, step, prior, Linv, A_g, A_m, blocks=(2,)):
+        """Tiles (Vs, n) of 128 rows of V_a for every property block a of `blocks` in lockstep (Vs: one tile per block) on the
+        transposed route, voxel order (iy, ix, iz): the generators of the step whose factor Linv is where it kept them, the others
+        from `prior`.  The rows of Z are formed once per tile and every operator term is ONE product for all the blocks (Z is
+        transformed once)."""
         sel_t, Md = step.sel_t, step.Md
         sp, N, Msp, T = self._spectral, self.N, self.Ms_pad, 128
         lat = (self._gram is not None and self._gram.edge_supported() and Msp == self.nx * self.ny and self.route.opt("z_lattice")
@@ -60,8 +64,12 @@ class SetStatisticsMixin:
         if not lat:
             Ag = self._resident_operator(A_g, "grav")
             Am = self._resident_operator(A_m, "magn")
-        gens = [step.gens[(0, 2)], step.gens[(1, 2)], sp.eigenvalues(prior.table(self, 2, 2))]
-        Zg, Zm, Zd, V, tmp = (self._workspace2d(nm, T, N) for nm in ("set_Zg", "set_Zm", "set_Zd", "set_V", "set_Vt"))
+        gen = lambda s_, a: step.gens[(s_, a)] if (s_, a) in step.gens else sp.eigenvalues(prior.table(self, s_, a))
+        gens = [[gen(s_, a) for a in blocks] for s_ in range(3)]
+        Zg, Zm, Zd = (self._workspace2d(nm, T, N) for nm in ("set_Zg", "set_Zm", "set_Zd"))
+        # (the drill block keeps the buffers it had before the other blocks came)
+        V = [self._workspace2d("set_V" if a == 2 else "set_V%d" % a, T, N) for a in blocks]
+        tmp = [self._workspace2d("set_Vt" if a == 2 else "set_Vt%d" % a, T, N) for a in blocks]
         Mv = 2 * Msp + Md
         for b0 in range(0, Mv, T):
             n = min(T, Mv - b0)
@@ -78,24 +86,26 @@ class SetStatisticsMixin:
                 Zd[:n].zero_()
                 Zd[:n, sel_t] = Linv[b0:b0 + n, 2 * Msp:2 * Msp + Md]
                 terms.append((Zd, gens[2]))
-            sp.product(terms[0][0], n, [terms[0][1]], [V])
+            sp.product(terms[0][0], n, terms[0][1], V)
             for Z, g in terms[1:]:
-                sp.product(Z, n, [g], [tmp])
-                V[:n].add_(tmp[:n])
+                sp.product(Z, n, g, tmp)
+                for v, t in zip(V, tmp):
+                    v[:n].add_(t[:n])
             yield V, n
 
-    def _vd_generic(self, step, prior, Linv, A_g, A_m, AK):
-        """Tiles (V, n) of 256 rows of V_d on any one-rank fp64 step, voxel order (iy, ix, iz)."""
+    def _v_generic(self, step, prior, Linv, A_g, A_m, AK, blocks=(2,)):
+        """Tiles (Vs, n) of 256 rows of V_a for every property block a of `blocks` on any one-rank fp64 step, voxel order
+        (iy, ix, iz).  Vs[i] holds N columns or more."""
         sel_t, Md = step.sel_t, step.Md
         N, Np, Msp, T = self.N, self.N_pad, self.Ms_pad, 256
         Mv = 2 * Msp + Md
         if AK is not None:
-            d0 = 2 * self.nc
-            AKd = AK[:, d0:d0 + Np]
-            V = self._workspace2d("set_V", T, Np)
+            AKa = [AK[:, a * self.nc:a * self.nc + Np] for a in blocks]
+            V = [self._workspace2d("set_V" if a == 2 else "set_V%d" % a, T, Np) for a in blocks]
             for b0 in range(0, Mv, T):
                 e = b0 + T                                  # (M_pad is a multiple of 256: whole tiles; columns >= e of L^-1 are zero)
-                hip.gemm_nn(Linv[b0:e, :e], AKd[:e], V)
+                for AKd, v in zip(AKa, V):
+                    hip.gemm_nn(Linv[b0:e, :e], AKd[:e], v)
                 yield V, min(T, Mv - b0)
             return
         smp = self._set_sampler(prior)
@@ -113,8 +123,29 @@ class SetStatisticsMixin:
             Zt[:, 2, :].zero_()
             if Md and b0 + n > 2 * Msp:
                 Zt[:, 2, :][:, sel_t] = Linv[b0:b0 + T, 2 * Msp:2 * Msp + Md]
-            KZ = smp.apply_K(Zt[:n])
-            yield KZ[:, 2, :], n
+            KZ = smp.apply_K(Zt[:n])                        # (all three properties come out of the one circulant product)
+            yield [KZ[:, a, :] for a in blocks], n
+
+    def _zsource(self, step, AK, source):
+        """The tile source of a sweep, "spectral" or "generic" ("auto": by the step's route); sets set_source."""
+        spectral_ok = self._zpath_ok(step, AK)
+        if source == "auto":
+            source = "spectral" if spectral_ok else "generic"
+        if source == "spectral" and not spectral_ok:
+            raise RuntimeError("the spectral source needs a step on the transposed route")
+        if source not in ("spectral", "generic"):
+            raise ValueError("source must be 'auto', 'spectral' or 'generic'")
+        self.set_source = source
+        return source
+
+    def _v_tiles(self, source, prior, AK, blocks=(2,)):
+        """Generator of the V tiles of the last step's factor from `source` ("spectral" or "generic")."""
+        last = self.last
+        Linv, step = last["Linv"], last["step"]
+        A_g, A_m = last["ops"]
+        if source == "spectral":
+            return self._v_spectral(step, prior, Linv, A_g, A_m, blocks)
+        return self._v_generic(step, prior, Linv, A_g, A_m, AK if last["AK_complete"] else None, blocks)
 
     def set_statistics(self, sets, kernelfunc, lengths, crossweights, gp_amp, gp_sigma, observed=None, source="auto"):
         """Posterior statistics of the drill property over C voxel sets, from the factor of the last posterior() step:
@@ -144,29 +175,15 @@ class SetStatisticsMixin:
                                         float(gp_sigma[2]) ** 2, observed, source, AK)
 
     def _set_statistics(self, sets, prior, sigma2, observed, source, AK):
-        last = self.last
-        Linv, step = last["Linv"], last["step"]
-        A_g, A_m = last["ops"]
         C_, k = sets.shape
         dev = self.device
         idx = torch.as_tensor(sets.astype(np.int32), device=dev)
         G = torch.zeros((C_, k, k), dtype=F64, device=dev)
-        spectral_ok = self._zpath_ok(step, AK)
-        if source == "auto":
-            source = "spectral" if spectral_ok else "generic"
-        if source == "spectral" and not spectral_ok:
-            raise RuntimeError("the spectral source needs a step on the transposed route")
-        if source not in ("spectral", "generic"):
-            raise ValueError("source must be 'auto', 'spectral' or 'generic'")
-        self.set_source = source
-        if source == "spectral":
-            tiles = self._vd_spectral(step, prior, Linv, A_g, A_m)
-        else:
-            tiles = self._vd_generic(step, prior, Linv, A_g, A_m, AK if last["AK_complete"] else None)
+        tiles = self._v_tiles(self._zsource(self.last["step"], AK, source), prior, AK)
 
         def sweep():
             first = True
-            for V, n in tiles:
+            for (V,), n in tiles:
                 hip.set_gram(idx, V, n, G, accumulate=not first, ncols=self.N)
                 first = False
         self._timed("set_sweep", 0.0, sweep)

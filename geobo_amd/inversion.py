@@ -591,6 +591,58 @@ class Inversion:
             out["info_gain"][valid], out["path_std"][valid], out["sum_var"][valid], out["status"][valid] = ig, np.sqrt(pv) * ds, sv * ds ** 2, st
         return out
 
+    # ---- block-support statistics ---------------------------------------------------------------------------
+    def block_statistics(self, block, write=False):
+        """Posterior mean and 3 x 3 covariance of the three properties' averages over the boxes of a block model, after cubing():
+        block = (bx, by, bz) voxels in the x, y, z order of the settings; the boxes tile the cube from its origin and are partial at the
+        far edges.  The factor of the current hyper-parameters is reused, or rebuilt (without the mean and variance) when the last
+        step used others.  Returns a dict of arrays in the cubes' (y, x, z) order and cubing()'s data units: `mean` (3, yB, xB, zB) the
+        box means of the mean cubes, `cov` (yB, xB, zB, 3, 3) the covariance of the three block means, `std` (3, yB, xB, zB) the roots
+        of its diagonal (NaN where an entry is negative), `corr` (yB, xB, zB, 3, 3), `count` (yB, xB, zB) voxels per block, `centre`
+        (yB, xB, zB, 3) x, y, z of the block centres.  The entries are raw: the reference's matern32 prior is not positive semidefinite,
+        so a block's matrix may be slightly indefinite and a correlation may pass 1 by a fraction of a percent; nothing is clipped.
+        Drill entries are NaN without drill data, as cubing()'s.  write=True: block_model.csv in outpath."""
+        from . import blocksupport
+        s = self.settings
+        bx, by, bz = blocksupport.check_box(block, (s.xNcube, s.yNcube, s.zNcube))
+        self._cubing_done("block_statistics()")
+        grid, box = (s.yNcube, s.xNcube, s.zNcube), (by, bx, bz)
+        self._ensure_factor()
+        lengths = create_cov_lengths(np.array(self.gp_length, dtype=float))
+        cov, _ = self.engine.block_covariance(box, s.kernelfunc, [float(v) for v in lengths], self.coeffm, self.gp_amp)
+        cov = cov.cpu().numpy()
+        index, count = blocksupport.block_partition(grid, box)
+        nb = blocksupport.block_counts(grid, box)
+        box_mean = lambda v: np.bincount(index, weights=np.asarray(v, dtype=np.float64).reshape(-1), minlength=count.size) / count
+        cs = self._cube_scale                               # (products in the survey's dtype, as cubing() squares them)
+        scale, scale2 = np.array([float(v) for v in cs]), np.array([[float(a * b) for b in cs] for a in cs])
+        with np.errstate(all="ignore"):
+            mean = np.stack([box_mean(self.mu_rec.reshape(3, -1)[i] * self._cube_scale[i]) for i in range(3)])
+            var = np.einsum("baa->ba", cov)
+            std_n = np.sqrt(np.where(var >= 0, var, np.nan))
+            corr = cov / np.sqrt(var[:, :, None] * var[:, None, :])
+            cov = cov * scale2
+            corr = np.where(np.isnan(cov), np.nan, corr)    # (NaN drill entries without drill data)
+            std = (std_n * scale[None, :]).T
+        out = dict(mean=mean.reshape((3,) + nb), cov=cov.reshape(nb + (3, 3)), std=std.reshape((3,) + nb), corr=corr.reshape(nb + (3, 3)),
+                   count=count.reshape(nb), centre=np.stack([box_mean(self.voxelpos[i]) for i in range(3)], axis=-1).reshape(nb + (3,)))
+        if write:
+            self._write_block_model(out)
+        return out
+
+    def _write_block_model(self, out):
+        """block_model.csv in outpath: one row per block."""
+        import os
+
+        import pandas as pd
+        names = ("DENSITY", "MAGSUS", "DRILL")
+        cols = dict(EASTING=out["centre"][..., 0], NORTHING=out["centre"][..., 1], DEPTH=out["centre"][..., 2], COUNT=out["count"])
+        cols.update({"MEAN_" + n: out["mean"][i] for i, n in enumerate(names)})
+        cols.update({"STD_" + n: out["std"][i] for i, n in enumerate(names)})
+        cols.update({"CORR_%s_%s" % (names[a], names[b]): out["corr"][..., a, b] for a, b in ((0, 1), (0, 2), (1, 2))})
+        pd.DataFrame({k: np.asarray(v).reshape(-1) for k, v in cols.items()}).to_csv(
+            os.path.join(self.settings.outpath, "block_model.csv"), index=False)
+
     def propose_drill_campaign(self, q, utility="information", costs=None, write=False):
         """A greedy batch of q distinct vertical holes ("kriging believer"): pick the best inner hole by `utility` ("information",
         "ucb", "ucb_path"; see geobo_amd.campaign), add its voxels that carry no drill row yet as drill rows whose values are the

@@ -41,6 +41,9 @@ def run(settings, method="auto", bayesopt=True, write=True):
     out = dict(zip(names, cubes), inversion=inv, drillcoord=drillcoord, inputs=(gravfield, magfield, drillfield, sensor_locations, drilldata0))
     if cv:
         out["cross_validation"] = cv_result
+    bm = getattr(s, "block_model", None)                  # optional YAML key block_model: [bx, by, bz] voxels per block
+    if bm:
+        out["block_model"] = inv.block_statistics(tuple(bm), write=write)
     nsamp = int(getattr(s, "posterior_samples", 0) or 0)     # optional YAML keys posterior_samples (default 0) and sample_seed
     if nsamp > 0:
         samples = inv.sample_posterior(nsamp, seed=int(getattr(s, "sample_seed", 0) or 0))

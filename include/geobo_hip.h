@@ -44,7 +44,8 @@ extern "C" {
  * Also additive since 212, version unchanged: the per-set posterior statistics of information.hip (geobo_set_gram,
  * geobo_set_logdet).
  * Also additive since 212, version unchanged: the cross-validation kernels of crossval.hip (geobo_kinv_diag,
- * geobo_kinv_diag_ws_bytes, geobo_set_loo). */
+ * geobo_kinv_diag_ws_bytes, geobo_set_loo) and the block-support kernel of blockcov.hip (geobo_block_cov,
+ * geobo_block_cov_ws_bytes). */
 
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
@@ -652,6 +653,22 @@ int geobo_kinv_diag(int64_t m, const double* Linv, int64_t ldl, const double* u,
  * (GEOBO_E_ARG).  C == 0 is a no-op. */
 int geobo_set_loo(int64_t C, int k, const double* G, const int32_t* idx, const double* alpha, int64_t n, double* out, double* resid,
                   double* var, double* white, int* status, void* stream);
+
+/* ---- block-support posterior statistics (blockcov.hip) -----------------------------------------------------
+ * Blocks of (by, bx, bz) voxels tile the (ny, nx, nz) grid from the origin, partial at the far edges: nb = ceil(n / b) per axis,
+ * block (jy, jx, jz) has index (jy nbx + jx) nbz + jz.  V0, V1, V2: R x ldv fp64 row-major, columns in voxel order (iy, ix, iz),
+ * ldv >= N = ny nx nz (columns >= N are never read).  With the box sums s_a[r, B] = sum_{v in B} Va[r, v] (not normalised),
+ *   C6[B][ab] = (accumulate ? C6[B][ab] : 0) + sum_{r < R} s_a[r, B] s_b[r, B],   ab in the order 00, 01, 02, 11, 12, 22,
+ * C6: nblocks x 6 fp64.  Every element of the three tiles is read once (16-byte loads where nz is even and the row's offset
+ * allows, 8-byte loads otherwise).  One wave per (block column x chunk of z, slice of rows); the slice length follows from the box
+ * alone; one slot of six partial sums per (slice, block) in ws, added in slice order by a finish pass, then the old value: no
+ * atomics, bitwise reproducible, independent of what ws held.  R == 0 zeroes C6, or does nothing when accumulating.
+ * geobo_block_cov_ws_bytes: the workspace of a call (a multiple of 16, at least 16), 0 for invalid arguments.  Checks before any
+ * device access (GEOBO_E_ARG): NULL pointers, R < 0, an extent or box edge < 1, a box edge beyond its extent, N > INT32_MAX,
+ * ldv < N, ws_bytes too small. */
+size_t geobo_block_cov_ws_bytes(int64_t R, int ny, int nx, int nz, int by, int bx, int bz);
+int geobo_block_cov(int64_t R, const double* V0, const double* V1, const double* V2, int64_t ldv, int ny, int nx, int nz, int by,
+                    int bx, int bz, int accumulate, double* C6, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
