@@ -61,8 +61,10 @@ struct GemmArgs {
   int ntiles;
   // batching (blockIdx.y) and store predicates (the compute tile grid may overhang the valid m x n region)
   int64_t sXb, sYb, sCb, m_valid, n_valid; int batch;
-  // generator
+  // generator: contraction points p (N_pad of them) and, in coordinate mode, the column points q of this launch as a second
+  // SoA -- a slice of the contraction set itself (geobo_ak_fused: q = p + col0) or any other point set (geobo_ak_points)
   const double *px, *py, *pz; int64_t gcol0;
+  const double *qx, *qy, *qz;
   CovParams cov;
   // lattice-table generator (Y_TAB): table[(|diy|*gnx + |dix|)*gnz + |diz|] = w*amp*k on the grid's difference lattice
   const double* table; int gnx, gny, gnz; int64_t gN;
@@ -275,8 +277,8 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) gemm_f64_kernel(const GemmArg
   const int gsub = __builtin_amdgcn_readfirstlane(tid / TN);
   v2d yr[EPT / 2];
   if constexpr (YMODE == Y_GEN) {
-    const int64_t q = a.gcol0 + col0 + gq;
-    qx = a.px[q]; qy = a.py[q]; qz = a.pz[q];
+    const int64_t q = col0 + gq;
+    qx = a.qx[q]; qy = a.qy[q]; qz = a.qz[q];
   }
 
   // lattice-table mode: per staged 16-byte slot this thread serves (q-row, k-pair); all index arithmetic is 32-bit
@@ -723,11 +725,34 @@ extern "C" int geobo_ak_fused(int kernel_id, const double* A, int64_t Ms_pad, in
   a.X = A; a.ldx = lda; a.Y = nullptr; a.ldy = 0; a.C = AK; a.ldc = ldak; a.k = N_pad;
   a.alpha = 1.0; a.beta = 0.0; a.tri = 0;
   a.px = x; a.py = y; a.pz = z; a.gcol0 = col0;
+  a.qx = x + col0; a.qy = y + col0; a.qz = z + col0;
   a.cov = make_cov(kernel_id, l1, l2, w, amp);
   hipStream_t st = (hipStream_t)stream;
 #define GEOBO_FUSED(ID) return launch_by_rows<Y_GEN, EPI_STORE, ID>(a, Ms_pad, ncols, st)
   COV_DISPATCH_ALL(kernel_id, GEOBO_FUSED);
 #undef GEOBO_FUSED
+  return GEOBO_E_ARG;
+}
+
+// The same launch with the column points taken from a point set of their own: the generator's q registers are loaded from
+// (qx, qy, qz) instead of a slice of the contraction set; chunking, LDS ring, generator / MFMA overlap and tile map are Y_GEN's.
+extern "C" int geobo_ak_points(int kernel_id, const double* A, int64_t R_pad, int64_t N_pad, int64_t lda,
+                               const double* px, const double* py, const double* pz,
+                               const double* qx, const double* qy, const double* qz, int64_t nq_pad,
+                               double l1, double l2, double w, double amp, double* out, int64_t ldo, void* stream) {
+  if (!A || !px || !py || !pz || !qx || !qy || !qz || !out) return GEOBO_E_ARG;
+  if (R_pad <= 0 || N_pad <= 0 || nq_pad <= 0 || R_pad % 128 || N_pad % BK || nq_pad % 128 || (lda & 1) || lda < N_pad || ldo < nq_pad)
+    return GEOBO_E_ALIGN;
+  GemmArgs a{};
+  a.X = A; a.ldx = lda; a.Y = nullptr; a.ldy = 0; a.C = out; a.ldc = ldo; a.k = N_pad;
+  a.alpha = 1.0; a.beta = 0.0; a.tri = 0;
+  a.px = px; a.py = py; a.pz = pz; a.gcol0 = 0;
+  a.qx = qx; a.qy = qy; a.qz = qz;
+  a.cov = make_cov(kernel_id, l1, l2, w, amp);
+  hipStream_t st = (hipStream_t)stream;
+#define GEOBO_POINTS(ID) return launch_by_rows<Y_GEN, EPI_STORE, ID>(a, R_pad, nq_pad, st)
+  COV_DISPATCH_ALL(kernel_id, GEOBO_POINTS);
+#undef GEOBO_POINTS
   return GEOBO_E_ARG;
 }
 

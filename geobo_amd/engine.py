@@ -46,6 +46,7 @@ from .transposed import TransposedPosteriorMixin
 from .information import SetStatisticsMixin
 from .crossval import CrossValidationMixin
 from .blocksupport import BlockSupportMixin
+from .pointpred import PointPredictionMixin
 from .step import Prior, Step
 from .sharding import (EmulatedGroup, allreduce_sum_, assemble_columns, backend_of, exchange_blocks, exchange_blocks_finish,
                        exchange_blocks_start, gather_rows, gather_slices, shard_columns)
@@ -129,7 +130,8 @@ def _on_device(fn):
     return wrapper
 
 
-class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixin, SetStatisticsMixin, CrossValidationMixin, BlockSupportMixin):
+class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixin, SetStatisticsMixin, CrossValidationMixin, BlockSupportMixin,
+                      PointPredictionMixin):
     def __init__(self, settings, device=None, rank=0, world=1, group=None, profile=False, method="auto", assembly="f64",
                  operators="resident"):
         """assembly "f32": covariance tables rounded through fp32 and A K kept in fp32 in HBM (BASELINE config 5, "fp32 kernel
@@ -1071,18 +1073,19 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         return C[idx][:, idx].cpu().numpy()
 
     # ---- posterior realisations (Matheron's rule) ------------------------------------------------------------
-    def _operator_rows(self, A):
-        """(r0, rows) batches of a forward operator: the resident matrix at once, a streamed one 256 zero-padded rows at a time."""
+    def _operator_rows(self, A, rows=256, slot="cond_op_rows"):
+        """(r0, rows) batches of a forward operator: the resident matrix at once, a streamed one 256 zero-padded rows at a time
+        (`rows`, a multiple of 128, at a time into workspace `slot` for a caller that wants another batch; never beyond row Ms_pad)."""
         if not isinstance(A, StreamedOperator):
             yield 0, A[:self.Ms_pad, :self.N_pad]
             return
-        buf = self._workspace2d("cond_op_rows", 256, self.N_pad)
-        for r0 in range(0, self.Ms, 256):
-            R = min(256, self.Ms - r0)
+        buf = self._workspace2d(slot, rows, self.N_pad)
+        for r0 in range(0, self.Ms, rows):
+            R = min(rows, self.Ms - r0)
             A.rows_into(buf, r0, R)
-            if R < 256:
+            if R < rows:
                 buf[R:].zero_()
-            yield r0, buf
+            yield r0, buf[:min(rows, self.Ms_pad - r0)]
 
     @_on_device
     def condition(self, F, eps, A_g, A_m, y_g, y_m, y_d, sampler):

@@ -320,6 +320,23 @@ def ak_fused(kid, A, xyz, col0, ncols, l1, l2, w, amp, out):
     return out
 
 
+def ak_points(kid, A, grid_xyz, q_xyz, l1, l2, w, amp, out):
+    """out[:, :nq] = A @ K(grid, Q): geobo_ak_fused's product against the nq column points q_xyz (three 1-D tensors, nq % 128 == 0)
+    instead of a slice of the contraction points grid_xyz."""
+    lib = require_gpu()
+    lda = _rowmajor(A, "A")
+    ldo = _rowmajor(out, "out")
+    x, y, z = (_chk(t, "grid_xyz") for t in grid_xyz)
+    qx, qy, qz = (_chk(t, "q_xyz") for t in q_xyz)
+    R_pad, N_pad = A.shape
+    nq = qx.numel()
+    assert min(x.numel(), y.numel(), z.numel()) >= N_pad and qy.numel() == nq and qz.numel() == nq
+    assert all(t.is_contiguous() for t in (x, y, z, qx, qy, qz)) and out.shape[0] >= R_pad and out.shape[1] >= nq
+    _lib.check(lib.geobo_ak_points(kid, _p(A), R_pad, N_pad, lda, _p(x), _p(y), _p(z), _p(qx), _p(qy), _p(qz), nq, float(l1),
+                                   float(l2), float(w), float(amp), _p(out), ldo, _stream()), "geobo_ak_points")
+    return out
+
+
 def cov_table(kid, nx, ny, nz, sx, sy, sz, l1, l2, w, amp, device="cuda"):
     """Covariance on the grid's difference lattice, z mirrored: (ny*nx*2nz,) tensor, index (diy*nx + dix)*2nz + (dz + nz-1)."""
     lib = require_gpu()

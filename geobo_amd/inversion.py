@@ -643,6 +643,105 @@ class Inversion:
         pd.DataFrame({k: np.asarray(v).reshape(-1) for k, v in cols.items()}).to_csv(
             os.path.join(self.settings.outpath, "block_model.csv"), index=False)
 
+    # ---- prediction at arbitrary points ---------------------------------------------------------------------
+    def to_covariance_frame(self, points):
+        """(Q, 3) points x, y, z in the cube's own coordinates (those of voxelpos) -> (3, Q) in the covariance frame, the frame of
+        calcGridPoints3D: a voxel centre lands on its grid point (i + 1) * voxel size."""
+        s = self.settings
+        p = np.asarray(points, dtype=np.float64)
+        return np.stack([p[:, 0] + s.xvoxsize / 2., p[:, 1] + s.yvoxsize / 2., (s.zmax - p[:, 2]) + s.zvoxsize / 2.])
+
+    def _check_points(self, points):
+        """`points` as a (Q, 3) float64 array inside the closed box of the cube; ValueError otherwise (naming the first offender)."""
+        s = self.settings
+        try:
+            p = np.array(points, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("points must be a (Q, 3) array of x, y, z") from None
+        if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise ValueError("points must be a (Q, 3) array of x, y, z with Q >= 1, got shape %r" % (p.shape,))
+        lo = np.array([0., 0., s.zmax - s.zLcube])
+        hi = np.array([s.xLcube, s.yLcube, s.zmax])
+        bad = ~((p >= lo) & (p <= hi)).all(axis=1)              # (a NaN coordinate is outside too)
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError("point %d = (%r, %r, %r) lies outside the cube [0, %r] x [0, %r] x [%r, %r]: no extrapolation"
+                             % (i, p[i, 0], p[i, 1], p[i, 2], hi[0], hi[1], lo[2], hi[2]))
+        return p
+
+    def predict_points(self, points, full_cov=False, batch=4096):
+        """Posterior of the three properties at arbitrary points inside the cube, after cubing(): `points` (Q, 3) x, y, z in the cube's
+        own coordinates (those of voxelpos), inside the closed box [0, xLcube] x [0, yLcube] x [zmax - zLcube, zmax].  The factor of the
+        current hyper-parameters is reused, or rebuilt when the last step used others.  Returns a dict in cubing()'s data units: `mean`
+        (3, Q), `var` (3, Q), `std` (3, Q; NaN where var < 0) and with full_cov `cov` (3Q, 3Q), ordered [property][point].  The values
+        are raw (the reference's matern32 prior is slightly indefinite); drill entries are NaN without drill data, as cubing()'s."""
+        self._cubing_done("predict_points()")
+        p = self._check_points(points)
+        self._ensure_factor()
+        eng = self.engine
+        from . import hip
+        q = tuple(hip.to_dev(np.ascontiguousarray(c), eng.device) for c in self.to_covariance_frame(p))
+        lengths = create_cov_lengths(np.array(self.gp_length, dtype=float))
+        r = eng.predict_points(q, self.settings.kernelfunc, [float(v) for v in lengths], self.coeffm, self.gp_amp, full_cov=full_cov,
+                               batch=batch)
+        Q = p.shape[0]
+        cs = self._cube_scale                               # (products in the survey's dtype, as cubing() squares them)
+        with np.errstate(all="ignore"):
+            mean = r[0].cpu().numpy() * np.array([float(v) for v in cs])[:, None]
+            var = r[1].cpu().numpy() * np.array([float(v * v) for v in cs])[:, None]
+            out = dict(mean=mean, var=var, std=np.sqrt(np.where(var >= 0, var, np.nan)))
+            if full_cov:
+                scale2 = np.array([[float(a * b) for b in cs] for a in cs])
+                out["cov"] = r[2].cpu().numpy() * np.repeat(np.repeat(scale2, Q, axis=0), Q, axis=1)
+        return out
+
+    def path_points(self, x0, y0, azimuth, dip, step=None, length=None):
+        """Points and ranges of a hole collared at (x0, y0, zmax) with azimuth / dip in degrees (the convention of
+        Acquisition.path_voxels): ranges step/2, 3 step/2, ... up to `length`, cut where the path first leaves the cube's box.
+        step defaults to half the smallest voxel edge, length to zLcube.  Returns ((n, 3) points, (n,) ranges)."""
+        from .acquisition import spherical2cartes
+        s = self.settings
+        step = 0.5 * min(s.xvoxsize, s.yvoxsize, s.zvoxsize) if step is None else float(step)
+        length = float(s.zLcube) if length is None else float(length)
+        if not (step > 0 and np.isfinite(step) and length > 0 and np.isfinite(length)):
+            raise ValueError("step and length must be positive, got %r and %r" % (step, length))
+        n = int(np.floor(length / step + 0.5 + 1e-12))          # ranges (k + 1/2) step <= length
+        rng = (np.arange(n) + 0.5) * step
+        x, y, z = spherical2cartes(float(x0), float(y0), float(s.zmax), np.deg2rad(azimuth), np.deg2rad(180. - dip), rng)
+        pts = np.stack([x, y, z], axis=1) if n else np.empty((0, 3))
+        lo = np.array([0., 0., s.zmax - s.zLcube])
+        hi = np.array([s.xLcube, s.yLcube, s.zmax])
+        inside = ((pts >= lo) & (pts <= hi)).all(axis=1)
+        keep = n if inside.all() else int(np.argmin(inside))    # cut at the first point outside
+        return pts[:keep], rng[:keep]
+
+    def predict_path(self, x0, y0, azimuth, dip, step=None, length=None):
+        """The prognosis log of a planned hole, after cubing(): the posterior at the points of path_points().  Returns dict(points
+        (n, 3), range (n,), mean (3, n), std (3, n), path_mean (3,) the average of each property along the hole, path_mean_std (3,)
+        = sqrt(1^T Sigma_aa 1) / n from the joint covariance of the points -- the uncertainty of the hole's average, which the
+        pointwise stds cannot give; NaN where that sum is negative).  ValueError when no point lies inside the cube."""
+        self._cubing_done("predict_path()")
+        pts, rng = self.path_points(x0, y0, azimuth, dip, step, length)
+        n = pts.shape[0]
+        if n == 0:
+            raise ValueError("the path from (%r, %r) with azimuth %r and dip %r has no point inside the cube" % (x0, y0, azimuth, dip))
+        r = self.predict_points(pts, full_cov=True)
+        with np.errstate(all="ignore"):
+            tot = np.array([r["cov"][a * n:(a + 1) * n, a * n:(a + 1) * n].sum() for a in range(3)])
+            pstd = np.sqrt(np.where(tot >= 0, tot, np.nan)) / n
+        return dict(points=pts, range=rng, mean=r["mean"], std=r["std"], path_mean=r["mean"].mean(axis=1), path_mean_std=pstd)
+
+    def _write_points_prediction(self, points, out, fname="points_prediction.csv"):
+        """points_prediction.csv in outpath: one row per point."""
+        import os
+
+        import pandas as pd
+        names = ("DENSITY", "MAGSUS", "DRILL")
+        cols = dict(X=points[:, 0], Y=points[:, 1], Z=points[:, 2])
+        cols.update({"MEAN_" + n: out["mean"][i] for i, n in enumerate(names)})
+        cols.update({"STD_" + n: out["std"][i] for i, n in enumerate(names)})
+        pd.DataFrame(cols).to_csv(os.path.join(self.settings.outpath, fname), index=False)
+
     def propose_drill_campaign(self, q, utility="information", costs=None, write=False):
         """A greedy batch of q distinct vertical holes ("kriging believer"): pick the best inner hole by `utility` ("information",
         "ucb", "ucb_path"; see geobo_amd.campaign), add its voxels that carry no drill row yet as drill rows whose values are the

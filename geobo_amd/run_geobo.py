@@ -44,6 +44,19 @@ def run(settings, method="auto", bayesopt=True, write=True):
     bm = getattr(s, "block_model", None)                  # optional YAML key block_model: [bx, by, bz] voxels per block
     if bm:
         out["block_model"] = inv.block_statistics(tuple(bm), write=write)
+    pp = getattr(s, "predict_points", None)               # optional YAML key predict_points: csv (in inpath) with columns X, Y, Z
+    if pp:
+        import pandas as pd
+        fname = pp if os.path.isabs(str(pp)) else os.path.join(s.inpath, str(pp))
+        pts = pd.read_csv(fname)[["X", "Y", "Z"]].to_numpy(dtype=np.float64)
+        out["points_prediction"] = inv.predict_points(pts)
+        if write:
+            inv._write_points_prediction(pts, out["points_prediction"])
+    path = getattr(s, "predict_path", None)               # optional YAML key predict_path: [x0, y0, azimuth, dip] of a planned hole
+    if path:
+        out["path_prediction"] = inv.predict_path(*[float(v) for v in path])
+        if write:
+            inv._write_points_prediction(out["path_prediction"]["points"], out["path_prediction"], fname="path_prediction.csv")
     nsamp = int(getattr(s, "posterior_samples", 0) or 0)     # optional YAML keys posterior_samples (default 0) and sample_seed
     if nsamp > 0:
         samples = inv.sample_posterior(nsamp, seed=int(getattr(s, "sample_seed", 0) or 0))

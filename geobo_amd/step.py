@@ -59,6 +59,18 @@ class Prior:
             out[:, :nc].add_(tmp)
         return out
 
+    def ak_points(self, eng, s, j, A, q_xyz, out):
+        """A_s K_sj(grid, Q) for the column points q_xyz (padded SoA in the covariance frame): the same product off the grid."""
+        from . import hip
+        terms = self.terms(s, j)
+        xyz = eng.grid_points()
+        hip.ak_points(terms[0][0], A, xyz, q_xyz, self.lengths[j], self.lengths[s], terms[0][1], self.amp, out)
+        for kid, w in terms[1:]:
+            tmp = eng._workspace2d("dak_points_tmp", out.shape[0], out.shape[1])
+            hip.ak_points(kid, A, xyz, q_xyz, self.lengths[j], self.lengths[s], w, self.amp, tmp)
+            out.add_(tmp)
+        return out
+
 
 @dataclass
 class Step:

@@ -173,6 +173,18 @@ int geobo_ak_fused(int kernel_id, const double* A, int64_t Ms_pad, int64_t N_pad
                    const double* x, const double* y, const double* z, int64_t col0, int64_t ncols,
                    double l1, double l2, double w, double amp, double* AK, int64_t ldak, void* stream);
 
+/* The same product against columns that are NOT part of the contraction set: prediction at arbitrary points Q,
+ *     out[r, c] = sum_p A[r, p] * (w*amp*k(|P_p - Q_c|^2; l1, l2)),   r < R_pad, c < nq_pad, p < N_pad
+ * The same kernels as geobo_ak_fused (one generator, the column coordinates come from the second point set), so with
+ * q = p + col0 the two entries return the same bits.  A is (R_pad x N_pad, lda) zero padded, px/py/pz have N_pad entries,
+ * qx/qy/qz nq_pad entries (padding = any finite point), out is (R_pad x nq_pad, ldo); R_pad % 128 == 0, N_pad % 16 == 0,
+ * nq_pad % 128 == 0, lda even.  Every covariance id is accepted.  GEOBO_E_ARG for a null pointer, GEOBO_E_ALIGN for a bad
+ * extent, both before any device call. */
+int geobo_ak_points(int kernel_id, const double* A, int64_t R_pad, int64_t N_pad, int64_t lda,
+                    const double* px, const double* py, const double* pz,
+                    const double* qx, const double* qy, const double* qz, int64_t nq_pad,
+                    double l1, double l2, double w, double amp, double* out, int64_t ldo, void* stream);
+
 /* Regular-grid form of the same product.  On the grid of calcGridPoints3D (kernels.py:27-42) every covariance is a
  * function of the index difference (|diy|,|dix|,|diz|), so the generator stage becomes an integer-indexed gather from
  * a lattice table (nx*ny*nz doubles, L2 resident) instead of exp/sqrt on the FP pipe that the fp64 MFMA also needs:
