@@ -961,6 +961,80 @@ def block_cov(V, R, grid, box, C6, accumulate=False, ws=None):
     return C6
 
 
+def _samples(F, name):
+    """(S, 3, n) fp64 CUDA tensor with unit element stride -> (S, n, sample stride, property stride)."""
+    _chk(F, name)
+    if F.dim() != 3 or F.shape[1] != 3 or F.stride(2) != 1:
+        raise ValueError("%s must be (S, 3, n) with unit element stride" % name)
+    return F.shape[0], F.shape[2], F.stride(0), F.stride(1)
+
+
+def box_means(F, grid, box, G=None, count=None):
+    """Means of the S realisations F (S, 3, N; voxel order (iy, ix, iz)) over the boxes of `box` = (by, bx, bz) voxels tiling `grid` =
+    (ny, nx, nz) from the origin (partial at the far edges; block index (jy nbx + jx) nbz + jz): returns (G (S, 3, nblocks) fp64,
+    count (nblocks,) int32).  With the box (1, 1, 1) G equals F bit for bit."""
+    lib = require_gpu()
+    S, n, ss, ps = _samples(F, "F")
+    grid, box = tuple(int(v) for v in grid), tuple(int(v) for v in box)
+    if n != grid[0] * grid[1] * grid[2]:
+        raise ValueError("F holds %d elements per property, the grid %r has %d" % (n, grid, grid[0] * grid[1] * grid[2]))
+    nblocks = 1
+    for m, b in zip(grid, box):
+        nblocks *= (m + max(b, 1) - 1) // max(b, 1)
+    if G is None:
+        G = torch.empty((S, 3, nblocks), dtype=F64, device=F.device)
+    if count is None:
+        count = torch.empty(nblocks, dtype=torch.int32, device=F.device)
+    _chk(G, "G")
+    _chk(count, "count", torch.int32)
+    assert G.is_contiguous() and tuple(G.shape) == (S, 3, nblocks) and count.is_contiguous() and count.numel() == nblocks
+    _lib.check(lib.geobo_box_means(S, _p(F), ss, ps, *grid, *box, _p(G), _p(count), _stream()), "geobo_box_means")
+    return G, count
+
+
+def cutoff_stats_ws_doubles(S, n, C):
+    nbytes = _lib.load().geobo_cutoff_stats_ws_bytes(int(S), int(n), int(C))
+    if nbytes == 0:
+        raise ValueError("cutoff_stats: invalid samples %r, elements %r or cutoffs %r" % (S, n, C))
+    return nbytes // 8
+
+
+def cutoff_stats(F, p, thresholds, lo=None, mask=None, weight=None, hits=None, ws=None):
+    """S cubes F (S, 3, n) against the ascending `thresholds` (host sequence of C <= 32 doubles, -inf allowed) of property p: element v
+    of sample s passes cutoff c when F[s, p, v] >= thresholds[c], F[s, q, v] >= lo[q] for the other two properties (lo: three host
+    doubles, -inf = not read; default all -inf) and mask[v] != 0 (mask: (n,) uint8 or None); NaN fails.  Returns (cnt (S, C) int64 =
+    sum of the weights (weight: (n,) int32, None = 1) of the passing elements, sum (S, C) fp64 = sum of weight x value); hits
+    ((C, n) int32 or None) is incremented by one per passing sample.  Bitwise reproducible, the same for any grouping of samples."""
+    lib = require_gpu()
+    S, n, ss, ps = _samples(F, "F")
+    t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    lo_h = np.ascontiguousarray(np.full(3, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1))
+    C_ = t.size
+    if lo_h.size != 3:
+        raise ValueError("lo holds one lower bound per property")
+    dev = F.device
+    if mask is not None:
+        _chk(mask, "mask", torch.uint8)
+        assert mask.is_contiguous() and mask.numel() == n
+    if weight is not None:
+        _chk(weight, "weight", torch.int32)
+        assert weight.is_contiguous() and weight.numel() == n
+    if hits is not None:
+        _chk(hits, "hits", torch.int32)             # (the kernel's uint32 counters: torch has no arithmetic on uint32)
+        assert hits.is_contiguous() and tuple(hits.shape) == (C_, n)
+    need = cutoff_stats_ws_doubles(S, n, C_)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=F64, device=dev)
+    cnt = torch.empty((S, C_), dtype=torch.int64, device=dev)
+    tot = torch.empty((S, C_), dtype=F64, device=dev)
+    null = C.c_void_p(None)
+    _lib.check(lib.geobo_cutoff_stats(S, _p(F), ss, ps, n, int(p), C_, t.ctypes.data_as(C.POINTER(C.c_double)),
+                                      lo_h.ctypes.data_as(C.POINTER(C.c_double)), null if mask is None else _p(mask),
+                                      null if weight is None else _p(weight), _p(cnt), _p(tot), null if hits is None else _p(hits),
+                                      _p(_chk(ws, "ws")), ws.numel() * 8, _stream()), "geobo_cutoff_stats")
+    return cnt, tot
+
+
 def mfma_f64_peak(blocks=1024, iters=20000):
     """Time the v_mfma_f64_16x16x4_f64 issue rate; returns TFLOP/s (4 waves/WG x 16 MFMA x 2048 flop per iter)."""
     lib = require_gpu()

@@ -403,11 +403,21 @@ class Inversion:
         Tests: prior = (n, 3, N) array of f, noise = (n, M) array of eps (rows grav | magn | drill) replace the generators."""
         if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
             raise RuntimeError("sample_posterior() conditions on the survey of cubing(): call cubing() first")
-        s = self.settings
+        parts, ws, es = [], [], []
+        for fp, w, e in self._posterior_batches(n, seed, start, approximate, batch, prior, noise):
+            parts.append(self._sample_cubes(fp, self._cube_scale))
+            ws.append(w.cpu().numpy())
+            es.append(e.cpu().numpy())
+        clipped = self._sampler_cache[1].clipped_fraction
+        self.sample_info = dict(noise=np.concatenate(es), w=np.concatenate(ws), clipped_fraction=clipped)
+        out = tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+        return out + (clipped,) if approximate else out
+
+    def _posterior_batches(self, n, seed=0, start=0, approximate=False, batch=None, prior=None, noise=None):
+        """The realisations start .. start + n - 1 of sample_posterior() as device batches, in order: yields (f_post (k, 3, N) in
+        normalised units, w (k, M), eps (k, M)) per batch, views of the batch's tensors cut to the requested realisations."""
         eng = self.engine
-        want = _hyper_key(self.gp_amp, create_cov_lengths(np.array(self.gp_length, dtype=float)), self.coeffm)
-        if getattr(self, "_step_params", None) != want or eng.last is None or tuple(eng.last["props"]) != (0, 1, 2):
-            self._run(self.gp_amp, self.gp_length, None, False, False)
+        self._ensure_factor()
         # (with the caller's f only the exact spectra of K are used: an indefinite prior is no obstacle there)
         smp = self._prior_sampler(approximate or prior is not None)
         A_g, A_m = self._operators()
@@ -427,19 +437,100 @@ class Inversion:
             i0, i1 = max(b0, start), min(b0 + nb, start + n)
             out[i0 - b0:i1 - b0] = np.asarray(a, dtype=np.float64)[i0 - start:i1 - start].reshape((i1 - i0,) + shape)
             return torch.as_tensor(out, device=eng.device)
-        parts, ws, es = [], [], []
         for b0 in range(lo, hi, batch):
             nb = min(batch, hi - b0)
             f = given(prior, b0, nb, (3, eng.N)) if prior is not None else smp.sample(b0, nb, seed=int(seed))
             e = given(noise, b0, nb, (M,)) if noise is not None else observation_noise(int(seed), b0, nb, M, device=eng.device) * sig_t
             fp, w = eng.condition(f, e, A_g, A_m, y_g, y_m, y_d, smp)
             i0, i1 = max(b0, start) - b0, min(b0 + nb, start + n) - b0
-            parts.append(self._sample_cubes(fp[i0:i1], self._cube_scale))
-            ws.append(w[i0:i1].cpu().numpy())
-            es.append(e[i0:i1].cpu().numpy())
-        self.sample_info = dict(noise=np.concatenate(es), w=np.concatenate(ws), clipped_fraction=smp.clipped_fraction)
-        out = tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
-        return out + (smp.clipped_fraction,) if approximate else out
+            yield fp[i0:i1], w[i0:i1], e[i0:i1]
+
+    # ---- grade-tonnage curves and exceedance probabilities ------------------------------------------------
+    def grade_tonnage(self, cutoffs, prop="drill", n=256, seed=0, start=0, batch=64, offset=0.0, require=None, region=None, block=None,
+                      voxel_probability=False, approximate=False, write=False):
+        """Grade-tonnage curves of property `prop` ("density" | "magsus" | "drill" or 0 | 1 | 2) from the n posterior realisations
+        sample_posterior(n, seed, start) of the last cubing() survey, reduced on the device: per realisation and cutoff the volume at
+        or above the cutoff and the quantity it holds.  `cutoffs` (at most 32, any order) are in cubing()'s units after adding
+        `offset`: the cubes are deviations from the data mean, so absolute grades take offset = drillfield.mean(); the value counted
+        is cube + offset.  require = {property: lower bound} asks the other properties, at the same support and in cube units (no
+        offset), to reach a bound as well; region is a boolean cube (yN, xN, zN) restricting the voxels.  block = (bx, by, bz) voxels
+        (the order of block_statistics): the realisations are first averaged over the boxes of that block model (selection at block
+        support; a block counts with its voxels) and region is (yB, xB, zB).  batch bounds device memory and changes no bit;
+        approximate as in sample_posterior.
+        Returns a dict: `cutoffs` (C,), `count` (n, C) int64 voxels, `volume` (n, C) m^3, `quantity` (n, C) = sum of value x voxel
+        volume, `grade` (n, C) = quantity / volume (NaN where nothing passes), `quantiles` = {"volume", "quantity", "grade"}, each (3, C)
+        with the 10 / 50 / 90 % quantiles over the realisations, with voxel_probability `probability` (C, yN, xN, zN) (or the block
+        shape) = the fraction of realisations in which the voxel passes, with approximate `clipped_fraction`.  write=True:
+        grade_tonnage.csv in outpath."""
+        from . import blocksupport, resources
+        s = self.settings
+        p = resources.property_index(prop)
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("grade_tonnage() reduces realisations of the survey of cubing(): call cubing() first")
+        scale = [float(v) for v in self._cube_scale]
+        bounds = {resources.property_index(k): float(v) for k, v in (require or {}).items()}
+        if p in bounds:
+            raise ValueError("require names the other properties: %r is the one the cutoffs apply to" % (prop,))
+        if self.drillfield.size == 0 and (p == 2 or 2 in bounds):
+            raise ValueError("the drill cubes are NaN without drill data: no cutoff on them")
+        lo = np.full(3, -np.inf)
+        for q, v in bounds.items():
+            if np.isnan(v):
+                raise ValueError("a lower bound of require is NaN")
+            lo[q] = v / scale[q]
+        cut = np.asarray(cutoffs, dtype=np.float64).reshape(-1)
+        t, order = resources.normalised_thresholds(cut, offset, self._cube_scale[p])
+        grid = (s.yNcube, s.xNcube, s.zNcube)
+        box, shape = None, grid
+        if block is not None:
+            bx, by, bz = blocksupport.check_box(block, (s.xNcube, s.yNcube, s.zNcube))
+            box = (by, bx, bz)
+            shape = blocksupport.block_counts(grid, box)
+        n, start = int(n), int(start)
+        if n < 1 or start < 0:
+            raise ValueError("n >= 1 realisations from start >= 0, got n = %r, start = %r" % (n, start))
+        eng = self.engine
+        mask = None
+        if region is not None:
+            region = np.asarray(region)
+            if region.dtype != np.bool_ or region.shape != tuple(shape):
+                raise ValueError("region must be a boolean array of shape %r, got %r %r" % (tuple(shape), region.dtype, region.shape))
+            mask = torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=eng.device)
+        nel = int(np.prod(shape))
+        hits = torch.zeros((t.size, nel), dtype=torch.int32, device=eng.device) if voxel_probability else None
+        cnts, sums = [], []
+        for fp, _, _ in self._posterior_batches(n, seed, start, approximate, batch):
+            c, v = eng.cutoff_statistics(fp, p, t, lo=lo, mask=mask, box=box, hits=hits)
+            cnts.append(c)
+            sums.append(v)
+        count = resources.caller_order(torch.cat(cnts).cpu().numpy(), order)
+        total = resources.caller_order(torch.cat(sums).cpu().numpy(), order)
+        out = dict(cutoffs=cut.copy())
+        out.update(resources.tonnage_tables(count, total, scale[p], offset, float(s.xvoxsize) * float(s.yvoxsize) * float(s.zvoxsize)))
+        if voxel_probability:
+            prob = hits.cpu().numpy().astype(np.float64) / n
+            out["probability"] = resources.caller_order(prob.T, order).T.reshape((t.size,) + tuple(shape))
+        if approximate:
+            out["clipped_fraction"] = self._sampler_cache[1].clipped_fraction
+        if write:
+            import os
+            resources.curve_frame(out).to_csv(os.path.join(s.outpath, "grade_tonnage.csv"), index=False)
+        return out
+
+    def exceedance_probability(self, cutoffs, prop="drill", offset=0.0):
+        """The analytic voxel-support counterpart of grade_tonnage()'s `probability`, from the mean and variance cubes of cubing():
+        Phi((mu + offset - c) / sigma) per cutoff, shape (C, yN, xN, zN), in cubing()'s units.  NaN where the variance is not positive
+        (and in the drill cubes without drill data); nothing is clipped.  Host only."""
+        from . import resources
+        p = resources.property_index(prop)
+        if not hasattr(self, "mu_rec") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("exceedance_probability() reads the mean and variance cubes of cubing(): call cubing() first")
+        s = self.settings
+        shape = (3, s.yNcube, s.xNcube, s.zNcube)
+        with np.errstate(all="ignore"):
+            mean = np.asarray(self.mu_rec).reshape(shape)[p] * self._cube_scale[p]
+            var = np.diag(self.cov_rec).reshape(shape)[p] * self._cube_scale[p] ** 2
+        return resources.exceedance_probability(mean, var, cutoffs, offset)
 
     # ---- drill-hole information gain and greedy campaigns (DESIGN.md section 13) ------------------------------------------------
     def _cubing_done(self, what):

@@ -65,7 +65,20 @@ def run(settings, method="auto", bayesopt=True, write=True):
             for c, n in zip(samples, ("density", "magsus", "drill")):
                 for k in range(nsamp):
                     dataio.create_vtkcube(c[k], origin, voxelsize, fname=os.path.join(s.outpath, "cube_%s_sample_%03d.vtk" % (n, k)))
-    ncamp = int(getattr(s, "drill_campaign", 0) or 0)      # optional YAML keys drill_campaign (q, default 0) and campaign_utility
+    gt = getattr(s, "grade_tonnage", None)                # optional YAML key grade_tonnage: {cutoffs, property, samples, offset, block,
+    if gt:                                                # voxel_probability}; sample_seed is shared with posterior_samples
+        prop = gt.get("property", "drill")
+        blk = tuple(gt["block"]) if gt.get("block") else None
+        res = inv.grade_tonnage(list(gt["cutoffs"]), prop=prop, n=int(gt.get("samples", 256)), seed=int(getattr(s, "sample_seed", 0) or 0),
+                                offset=float(gt.get("offset", 0.0)), block=blk, voxel_probability=bool(gt.get("voxel_probability", False)),
+                                write=write)
+        out["grade_tonnage"] = res
+        if write and "probability" in res:
+            from .resources import PROPS, property_index
+            size = voxelsize if blk is None else tuple(v * b for v, b in zip(voxelsize, blk))
+            for k, cube in enumerate(res["probability"]):
+                dataio.create_vtkcube(cube, origin, size, fname=os.path.join(s.outpath, "cube_%s_exceed_%d.vtk" % (PROPS[property_index(prop)], k)))
+    ncamp = int(getattr(s, "drill_campaign", 0) or 0)     # optional YAML keys drill_campaign (q, default 0) and campaign_utility
     if ncamp > 0:
         out["drill_campaign"] = inv.propose_drill_campaign(ncamp, utility=getattr(s, "campaign_utility", None) or "information", write=write)
     if bayesopt:

@@ -45,7 +45,9 @@ extern "C" {
  * geobo_set_logdet).
  * Also additive since 212, version unchanged: the cross-validation kernels of crossval.hip (geobo_kinv_diag,
  * geobo_kinv_diag_ws_bytes, geobo_set_loo) and the block-support kernel of blockcov.hip (geobo_block_cov,
- * geobo_block_cov_ws_bytes). */
+ * geobo_block_cov_ws_bytes).
+ * Also additive since 212, version unchanged: the grade-tonnage reductions of gradetonnage.hip (geobo_box_means,
+ * geobo_cutoff_stats, geobo_cutoff_stats_ws_bytes). */
 
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
@@ -681,6 +683,39 @@ int geobo_set_loo(int64_t C, int k, const double* G, const int32_t* idx, const d
 size_t geobo_block_cov_ws_bytes(int64_t R, int ny, int nx, int nz, int by, int bx, int bz);
 int geobo_block_cov(int64_t R, const double* V0, const double* V1, const double* V2, int64_t ldv, int ny, int nx, int nz, int by,
                     int bx, int bz, int accumulate, double* C6, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- grade-tonnage reductions over realisations (gradetonnage.hip) -----------------------------------------
+ * Realisations F[s][a][v]: s < S samples sstride elements apart, a = 0, 1, 2 properties pstride elements apart, fp64,
+ * pstride >= the elements of a property, sstride >= 2 pstride + those elements.
+ *
+ * geobo_box_means: G[s][a][B] = the arithmetic mean of F[s][a][v] over the voxels of block B and count[B] = its voxels (int32), for
+ * the partition of geobo_block_cov (boxes of (by, bx, bz) voxels tiling the (ny, nx, nz) grid from the origin, partial at the far
+ * edges, block index (jy nbx + jx) nbz + jz; voxel order (iy, ix, iz)).  G: S x 3 x nblocks contiguous.  Every element is read once
+ * (16-byte loads where the address allows).  One lane per output; the sum runs along z within a z-segment of the box, then over the
+ * segments in ascending (iy, ix), each sum started by its first term: independent of S and of the launch, and with the box (1, 1, 1)
+ * G equals F bit for bit.  S == 0 is a no-op.  Checks before any device access (GEOBO_E_ARG): NULL pointers, S < 0, an extent or box
+ * edge < 1, a box edge beyond its extent, N > INT32_MAX, strides too small. */
+int geobo_box_means(int64_t S, const double* F, int64_t sstride, int64_t pstride, int ny, int nx, int nz, int by, int bx, int bz,
+                    double* G, int32_t* count, void* stream);
+
+/* geobo_cutoff_stats: S cubes of n elements per property against C thresholds in one pass.  t: C thresholds and lo: three lower
+ * bounds, both HOST arrays (they travel as kernel arguments); t ascending (equal neighbours and -inf allowed), 1 <= C <= 32.
+ * Element v of sample s PASSES cutoff c when F[s][p][v] >= t[c], F[s][q][v] >= lo[q] for the two properties q != p (lo[q] = -inf:
+ * property q is not read; lo[p] is not used) and mask[v] != 0 (mask: n uint8 or NULL).  A NaN fails every comparison.  With the
+ * weights w[v] (weight: n int32, or NULL for 1),
+ *   cnt[s][c] = sum_v w[v] [passes]   (int64, exact),     sum[s][c] = sum_v w[v] F[s][p][v] [passes]   (S x C each),
+ *   hits[c][v] += sum_s [passes]      (C x n uint32 or NULL; the caller zeroes it once and accumulates over calls).
+ * A workgroup owns 512 consecutive elements and walks the samples; one partial count and sum per (sample, chunk, c) in ws, added
+ * in chunk order by a finish pass: the order of every sum follows from n alone -- no floating-point atomics, bitwise reproducible,
+ * the same whether a sample is reduced alone or with others, independent of what ws held.  A hits entry has one owning lane: no
+ * atomics.  16-byte loads where the address allows, 8-byte loads otherwise (odd n, odd strides).  S == 0 is a no-op.
+ * geobo_cutoff_stats_ws_bytes: the workspace of a call (a multiple of 16, at least 16), 0 for invalid arguments.  Checks before any
+ * device access (GEOBO_E_ARG): NULL F, t, lo, cnt, sum or ws, S < 0, n < 1, C < 1, C > 32, p outside 0..2, a NaN in t or lo, t not
+ * ascending, strides too small, ws_bytes too small, ws not 16-byte aligned. */
+size_t geobo_cutoff_stats_ws_bytes(int64_t S, int64_t n, int C);
+int geobo_cutoff_stats(int64_t S, const double* F, int64_t sstride, int64_t pstride, int64_t n, int p, int C, const double* t,
+                       const double* lo, const uint8_t* mask, const int32_t* weight, int64_t* cnt, double* sum, uint32_t* hits,
+                       void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
