@@ -1035,6 +1035,76 @@ def cutoff_stats(F, p, thresholds, lo=None, mask=None, weight=None, hits=None, w
     return cnt, tot
 
 
+BODIES_INIT, BODIES_MERGE, BODIES_FLATTEN, BODIES_STATS, BODIES_ALL, BODIES_TILED = 1, 2, 4, 8, 15, 16
+BODY_STATS = ("count_total", "n_bodies", "largest_count", "largest_label", "seeded_count", "seeded_bodies")     # columns of stats
+BODY_SUMS = ("total", "largest", "seeded")                                                                       # columns of sums
+
+
+def bodies_ws_doubles(S, grid, C):
+    nbytes = _lib.load().geobo_bodies_ws_bytes(int(S), *[int(v) for v in grid], int(C))
+    if nbytes == 0:
+        raise ValueError("bodies: invalid samples %r, grid %r or cutoffs %r (samples x cutoffs <= 65535)" % (S, tuple(grid), C))
+    return nbytes // 8
+
+
+def bodies(F, grid, p, thresholds, lo=None, mask=None, weight=None, neighbours=6, min_count=1, seeds=None, hits_largest=None,
+           hits_seeded=None, labels=None, info=None, ws=None, phases=BODIES_ALL, stats=None, sums=None, tiled=True):
+    """Connected bodies of the cutoff sets of S cubes F (S, 3, n) on `grid` = (ny, nx, nz), n = ny nx nz: the set of (s, c) is that of
+    cutoff_stats (same thresholds, lo, mask, weight); bodies are its components under `neighbours` = 6 or 26.  seeds: host sequence of
+    K voxel indices or None.  Returns (stats (S, C, 6) int64 -- the columns BODY_STATS --, sums (S, C, 3) fp64 -- BODY_SUMS --, info
+    (one int32 on the device: 0 unless a bounded walk ran out, which the caller turns into an error)).  hits_largest, hits_seeded:
+    (C, n) int32 or None, incremented per sample whose largest / seeded body holds the voxel; labels: (S, C, n) int32 or None, the
+    smallest voxel index of each voxel's body, -1 outside.  Exact counts, bitwise reproducible sums.  tiled=False: the merge stage
+    without its tile-local phase in LDS (the same results, slower)."""
+    lib = require_gpu()
+    S, n, ss, ps = _samples(F, "F")
+    grid = tuple(int(v) for v in grid)
+    if len(grid) != 3 or n != grid[0] * grid[1] * grid[2]:
+        raise ValueError("F holds %d elements per property, the grid %r does not" % (n, grid))
+    t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    lo_h = np.ascontiguousarray(np.full(3, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1))
+    C_ = t.size
+    if lo_h.size != 3:
+        raise ValueError("lo holds one lower bound per property")
+    dev = F.device
+    if mask is not None:
+        _chk(mask, "mask", torch.uint8)
+        assert mask.is_contiguous() and mask.numel() == n
+    if weight is not None:
+        _chk(weight, "weight", torch.int32)
+        assert weight.is_contiguous() and weight.numel() == n
+    for h, name in ((hits_largest, "hits_largest"), (hits_seeded, "hits_seeded")):
+        if h is not None:
+            _chk(h, name, torch.int32)                # (the kernel's uint32 counters: torch has no arithmetic on uint32)
+            assert h.is_contiguous() and tuple(h.shape) == (C_, n)
+    if labels is not None:
+        _chk(labels, "labels", torch.int32)
+        assert labels.is_contiguous() and tuple(labels.shape) == (S, C_, n)
+    sd = np.ascontiguousarray(np.zeros(0, dtype=np.int32) if seeds is None else np.asarray(seeds, dtype=np.int32).reshape(-1))
+    need = bodies_ws_doubles(S, grid, C_)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=F64, device=dev)
+    if info is None:
+        info = torch.zeros(1, dtype=torch.int32, device=dev)
+    _chk(info, "info", torch.int32)
+    if stats is None:
+        stats = torch.empty((S, C_, len(BODY_STATS)), dtype=torch.int64, device=dev)
+    if sums is None:
+        sums = torch.empty((S, C_, len(BODY_SUMS)), dtype=F64, device=dev)
+    _chk(stats, "stats", torch.int64)
+    _chk(sums, "sums")
+    assert stats.is_contiguous() and tuple(stats.shape) == (S, C_, 6) and sums.is_contiguous() and tuple(sums.shape) == (S, C_, 3)
+    null = C.c_void_p(None)
+    opt = lambda x: null if x is None else _p(x)
+    _lib.check(lib.geobo_bodies(S, _p(F), ss, ps, *grid, int(p), C_, t.ctypes.data_as(C.POINTER(C.c_double)),
+                                lo_h.ctypes.data_as(C.POINTER(C.c_double)), opt(mask), opt(weight), int(neighbours), int(min_count), sd.size,
+                                sd.ctypes.data_as(C.POINTER(C.c_int32)), _p(stats), _p(sums), opt(hits_largest), opt(hits_seeded), opt(labels),
+                                _p(info), int(phases) | (BODIES_TILED if tiled else 0), _p(_chk(ws, "ws")), ws.numel() * 8, _stream()), "geobo_bodies")
+    if sd.size and (phases & BODIES_STATS):
+        torch.cuda.current_stream().synchronize()     # the staging copy of the host seeds has been read before `sd` goes away
+    return stats, sums, info
+
+
 def mfma_f64_peak(blocks=1024, iters=20000):
     """Time the v_mfma_f64_16x16x4_f64 issue rate; returns TFLOP/s (4 waves/WG x 16 MFMA x 2048 flop per iter)."""
     lib = require_gpu()

@@ -532,6 +532,119 @@ class Inversion:
             var = np.diag(self.cov_rec).reshape(shape)[p] * self._cube_scale[p] ** 2
         return resources.exceedance_probability(mean, var, cutoffs, offset)
 
+    # ---- connected ore bodies -----------------------------------------------------------------------------
+    def geobodies(self, cutoffs, prop="drill", n=256, seed=0, start=0, batch=64, offset=0.0, require=None, region=None, block=None,
+                  neighbours=6, min_voxels=1, seeds=None, probability=None, approximate=False, write=False):
+        """Connected bodies of the material at or above each cutoff, per posterior realisation, labelled and reduced on the device.
+        cutoffs, prop, n, seed, start, batch, offset, require, region, block and approximate are those of grade_tonnage(): the sets are
+        the same, so `count` equals grade_tonnage()'s.  neighbours: 6 (voxels joined by faces) or 26 (faces, edges, corners);
+        min_voxels: the bodies counted in `n_bodies` hold at least that many voxels (at block support: voxels of their blocks).
+        seeds: None, "drill" (the drilled voxels of cubing()), a boolean cube (yN, xN, zN) or a (K, 3) integer array of (ix, iy, iz);
+        at block support a seed stands for its block.  The SEEDED body of a realisation is the union of the bodies that hold a seed
+        which itself passes the cutoff.  probability: None, "largest", "seeded" or "both".
+        Returns a dict with columns in the caller's cutoff order: `cutoffs` (C,), `n_bodies` (n, C), `count` (n, C), `largest` and
+        `seeded` = dicts of `count`, `volume` (m^3), `quantity` and `grade` (n, C each; grade NaN when the body is empty),
+        `largest["label"]` (the body's smallest flat voxel or block index, -1 when empty), `seeded["bodies"]` (how many bodies hold a
+        seed), `quantiles` = {"n_bodies", "largest_volume", "seeded_volume"}, each (3, C) with the 10 / 50 / 90 % quantiles over
+        the realisations, `probability_largest` / `probability_seeded` (C, yN, xN, zN) (or the block shape) = the fraction of
+        realisations in which the voxel lies in that body, and with approximate `clipped_fraction`.  write=True: geobodies.csv in
+        outpath."""
+        from . import blocksupport, geobodies as gb, resources
+        s = self.settings
+        p = resources.property_index(prop)
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("geobodies() labels realisations of the survey of cubing(): call cubing() first")
+        neighbours = gb.check_neighbours(neighbours)
+        want_l, want_s = gb.check_probability(probability)
+        scale = [float(v) for v in self._cube_scale]
+        bounds = {resources.property_index(k): float(v) for k, v in (require or {}).items()}
+        if p in bounds:
+            raise ValueError("require names the other properties: %r is the one the cutoffs apply to" % (prop,))
+        if self.drillfield.size == 0 and (p == 2 or 2 in bounds):
+            raise ValueError("the drill cubes are NaN without drill data: no cutoff on them")
+        lo = np.full(3, -np.inf)
+        for q, v in bounds.items():
+            if np.isnan(v):
+                raise ValueError("a lower bound of require is NaN")
+            lo[q] = v / scale[q]
+        cut = np.asarray(cutoffs, dtype=np.float64).reshape(-1)
+        t, order = resources.normalised_thresholds(cut, offset, self._cube_scale[p])
+        grid = (s.yNcube, s.xNcube, s.zNcube)
+        sd = gb.parse_seeds(seeds, grid, drill=self._drill_selection() if isinstance(seeds, str) and seeds == "drill" else None)
+        box, shape = None, grid
+        if block is not None:
+            bx, by, bz = blocksupport.check_box(block, (s.xNcube, s.yNcube, s.zNcube))
+            box = (by, bx, bz)
+            shape = blocksupport.block_counts(grid, box)
+            sd = gb.seeds_to_blocks(sd, grid, box)
+        n, start, min_voxels = int(n), int(start), int(min_voxels)
+        if n < 1 or start < 0:
+            raise ValueError("n >= 1 realisations from start >= 0, got n = %r, start = %r" % (n, start))
+        if min_voxels < 1:
+            raise ValueError("min_voxels >= 1, got %r" % (min_voxels,))
+        eng = self.engine
+        mask = None
+        if region is not None:
+            region = np.asarray(region)
+            if region.dtype != np.bool_ or region.shape != tuple(shape):
+                raise ValueError("region must be a boolean array of shape %r, got %r %r" % (tuple(shape), region.dtype, region.shape))
+            mask = torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=eng.device)
+        nel = int(np.prod(shape))
+        hits_l = torch.zeros((t.size, nel), dtype=torch.int32, device=eng.device) if want_l else None
+        hits_s = torch.zeros((t.size, nel), dtype=torch.int32, device=eng.device) if want_s else None
+        stats, sums = [], []
+        for fp, _, _ in self._posterior_batches(n, seed, start, approximate, batch):
+            st, sm = eng.body_statistics(fp, p, t, lo=lo, mask=mask, box=box, neighbours=neighbours, min_count=min_voxels, seeds=sd,
+                                         hits_largest=hits_l, hits_seeded=hits_s)
+            stats.append(st)
+            sums.append(sm)
+        inv_order = np.empty_like(order)
+        inv_order[order] = np.arange(order.size)
+        stats = torch.cat(stats).cpu().numpy()[:, inv_order]
+        sums = torch.cat(sums).cpu().numpy()[:, inv_order]
+        out = dict(cutoffs=cut.copy())
+        out.update(gb.body_tables(stats, sums, scale[p], offset, float(s.xvoxsize) * float(s.yvoxsize) * float(s.zvoxsize)))
+        for name, hits in (("probability_largest", hits_l), ("probability_seeded", hits_s)):
+            if hits is not None:
+                prob = hits.cpu().numpy().astype(np.float64) / n
+                out[name] = prob[inv_order].reshape((t.size,) + tuple(shape))
+        if approximate:
+            out["clipped_fraction"] = self._sampler_cache[1].clipped_fraction
+        if write:
+            import os
+            gb.bodies_frame(out).to_csv(os.path.join(s.outpath, "geobodies.csv"), index=False)
+        return out
+
+    def label_bodies(self, cube, cutoff, neighbours=6, region=None):
+        """Connected bodies of {cube >= cutoff} for any (yN, xN, zN) cube -- a mean cube, one realisation -- labelled on the device:
+        (labels, sizes), labels (yN, xN, zN) int32 with the bodies numbered 1 .. B in ascending order of their smallest flat voxel
+        index and 0 outside (the numbering of scipy.ndimage.label), sizes (B,) the voxels of each.  NaN is outside; region: a
+        boolean cube restricting the voxels."""
+        from . import geobodies as gb
+        s = self.settings
+        grid = (s.yNcube, s.xNcube, s.zNcube)
+        neighbours = gb.check_neighbours(neighbours)
+        cube = np.asarray(cube, dtype=np.float64)
+        if cube.shape != grid:
+            raise ValueError("cube must have the shape %r, got %r" % (grid, cube.shape))
+        cutoff = float(cutoff)
+        if np.isnan(cutoff):
+            raise ValueError("the cutoff is NaN")
+        eng = self.engine
+        N = cube.size
+        mask = None
+        if region is not None:
+            region = np.asarray(region)
+            if region.dtype != np.bool_ or region.shape != grid:
+                raise ValueError("region must be a boolean array of shape %r, got %r %r" % (grid, region.dtype, region.shape))
+            mask = torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=eng.device)
+        F = torch.zeros((1, 3, N), dtype=torch.float64, device=eng.device)
+        F[0, 0] = torch.as_tensor(cube.reshape(-1).copy(), device=eng.device)
+        labels = torch.empty((1, 1, N), dtype=torch.int32, device=eng.device)
+        eng.body_statistics(F, 0, [cutoff], mask=mask, neighbours=neighbours, labels=labels)
+        numbered, sizes = gb.renumber(labels.cpu().numpy().reshape(grid))
+        return numbered, sizes
+
     # ---- drill-hole information gain and greedy campaigns (DESIGN.md section 13) ------------------------------------------------
     def _cubing_done(self, what):
         if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):

@@ -78,6 +78,22 @@ def run(settings, method="auto", bayesopt=True, write=True):
             size = voxelsize if blk is None else tuple(v * b for v, b in zip(voxelsize, blk))
             for k, cube in enumerate(res["probability"]):
                 dataio.create_vtkcube(cube, origin, size, fname=os.path.join(s.outpath, "cube_%s_exceed_%d.vtk" % (PROPS[property_index(prop)], k)))
+    gbd = getattr(s, "geobodies", None)                   # optional YAML key geobodies: {cutoffs, property, samples, offset, block,
+    if gbd:                                               # neighbours, min_voxels, seeds: drill, probability}; sample_seed is shared
+        prop = gbd.get("property", "drill")
+        blk = tuple(gbd["block"]) if gbd.get("block") else None
+        res = inv.geobodies(list(gbd["cutoffs"]), prop=prop, n=int(gbd.get("samples", 256)), seed=int(getattr(s, "sample_seed", 0) or 0),
+                            offset=float(gbd.get("offset", 0.0)), block=blk, neighbours=int(gbd.get("neighbours", 6)),
+                            min_voxels=int(gbd.get("min_voxels", 1)), seeds=gbd.get("seeds") or None,
+                            probability=gbd.get("probability") or None, write=write)
+        out["geobodies"] = res
+        if write:
+            from .resources import PROPS, property_index
+            size = voxelsize if blk is None else tuple(v * b for v, b in zip(voxelsize, blk))
+            # (one cube per cutoff: the seeded body's probability when asked for, else the largest body's)
+            cubes_p = res.get("probability_seeded", res.get("probability_largest"))
+            for k, cube in enumerate(cubes_p if cubes_p is not None else ()):
+                dataio.create_vtkcube(cube, origin, size, fname=os.path.join(s.outpath, "cube_%s_connected_%d.vtk" % (PROPS[property_index(prop)], k)))
     ncamp = int(getattr(s, "drill_campaign", 0) or 0)     # optional YAML keys drill_campaign (q, default 0) and campaign_utility
     if ncamp > 0:
         out["drill_campaign"] = inv.propose_drill_campaign(ncamp, utility=getattr(s, "campaign_utility", None) or "information", write=write)

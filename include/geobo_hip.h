@@ -47,7 +47,8 @@ extern "C" {
  * geobo_kinv_diag_ws_bytes, geobo_set_loo) and the block-support kernel of blockcov.hip (geobo_block_cov,
  * geobo_block_cov_ws_bytes).
  * Also additive since 212, version unchanged: the grade-tonnage reductions of gradetonnage.hip (geobo_box_means,
- * geobo_cutoff_stats, geobo_cutoff_stats_ws_bytes). */
+ * geobo_cutoff_stats, geobo_cutoff_stats_ws_bytes).
+ * Also additive since 212, version unchanged: the connected bodies of geobodies.hip (geobo_bodies, geobo_bodies_ws_bytes). */
 
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
@@ -716,6 +717,41 @@ size_t geobo_cutoff_stats_ws_bytes(int64_t S, int64_t n, int C);
 int geobo_cutoff_stats(int64_t S, const double* F, int64_t sstride, int64_t pstride, int64_t n, int p, int C, const double* t,
                        const double* lo, const uint8_t* mask, const int32_t* weight, int64_t* cnt, double* sum, uint32_t* hits,
                        void* ws, size_t ws_bytes, void* stream);
+
+/* ---- connected bodies of the cutoff sets (geobodies.hip) --------------------------------------------------
+ * geobo_bodies: the realisations, thresholds, bounds, mask and weights of geobo_cutoff_stats on the (ny, nx, nz) grid (voxel order
+ * (iy, ix, iz), n = ny nx nz).  Volume (s, c) holds the SET of the voxels that pass cutoff c in sample s (the predicate of
+ * geobo_cutoff_stats, so the totals agree exactly); a BODY is a connected component of it under `neighbours` = 6 (faces) or 26
+ * (faces, edges, corners).  The label of a body is its smallest voxel index.  t, lo and seeds are HOST arrays: t and lo travel as
+ * kernel arguments; the K seed voxel indices (int32, 0 <= K <= n, NULL allowed for K = 0) are checked here and staged into the
+ * workspace by a copy on `stream`, so the array stays unchanged until the stream has passed the call.
+ *   stats[s][c][6] (int64): 0 the weighted voxels of the set (= geobo_cutoff_stats's cnt), 1 the bodies of at least min_count
+ *     weighted voxels, 2 the count and 3 the label of the largest body (a tie goes to the smaller label; 0 and -1 for an empty
+ *     set), 4 the count of the SEEDED body -- the union of the bodies that hold a seed which is itself in the set -- and 5 the
+ *     number of those bodies;
+ *   sums[s][c][3] (fp64): the sum of w x over the set (= geobo_cutoff_stats's sum, bit for bit), the largest and the seeded body;
+ *   hits_largest, hits_seeded[c][v] (C x n uint32, or NULL) += the samples of the call in which v lies in that body; the caller
+ *     zeroes them once and accumulates over calls; one owning lane per entry, no atomics;
+ *   labels[s][c][v] (S x C x n int32, or NULL): the label of v's body, -1 outside the set;
+ *   info (one int32 on the device, zeroed by the caller): stays 0; a walk of the union-find that did not end within 2 n + 64 rounds
+ *     leaves 1 (find), 2 (union), 3 (flatten) or 4 (tile) there and the results of the call are undefined.  No loop is unbounded.
+ * Union-find per volume on int32 parents with L[x] <= x, lowered only by agent-scope atomic minima, in separate launches (init,
+ * merge, flatten, statistics); `phases` is the sum of the GEOBO_BODIES_* stages to run, GEOBO_BODIES_ALL for a whole call -- a
+ * timing harness runs the stages of one call one after the other on the same workspace.  With GEOBO_BODIES_TILED added, the merge
+ * stage first labels tiles of at most 512 voxels in LDS (the same find / union on workgroup-scope atomics) and then unites across
+ * tile faces only; labels and statistics are the same bit for bit, the stage is faster.  Counts are exact (integer atomics); the
+ * floating-point sums use no atomics and the chunk order of geobo_cutoff_stats: bitwise reproducible, the same whether a sample
+ * or a cutoff is reduced alone or with others.  S == 0 is a no-op.
+ * geobo_bodies_ws_bytes: the workspace of a call (a multiple of 16), 0 for invalid arguments.  Checks before any device access
+ * (GEOBO_E_ARG): NULL F, t, lo, stats, sums, info or ws, S < 0, S C > 65535, an extent < 1, n > INT32_MAX, C < 1, C > 32, p outside
+ * 0..2, neighbours not 6 or 26, min_count < 1, K < 0, K > n, K > 0 without seeds, a seed outside 0..n-1, a NaN in t or lo, t not
+ * ascending, strides too small, phases without a stage or outside 1..31, ws_bytes too small, ws not 16-byte aligned. */
+enum { GEOBO_BODIES_INIT = 1, GEOBO_BODIES_MERGE = 2, GEOBO_BODIES_FLATTEN = 4, GEOBO_BODIES_STATS = 8, GEOBO_BODIES_ALL = 15, GEOBO_BODIES_TILED = 16 };
+size_t geobo_bodies_ws_bytes(int64_t S, int ny, int nx, int nz, int C);
+int geobo_bodies(int64_t S, const double* F, int64_t sstride, int64_t pstride, int ny, int nx, int nz, int p, int C, const double* t,
+                 const double* lo, const uint8_t* mask, const int32_t* weight, int neighbours, int64_t min_count, int64_t K,
+                 const int32_t* seeds, int64_t* stats, double* sums, uint32_t* hits_largest, uint32_t* hits_seeded, int32_t* labels,
+                 int32_t* info, int phases, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
