@@ -49,6 +49,7 @@ from .blocksupport import BlockSupportMixin
 from .pointpred import PointPredictionMixin
 from .resources import ResourceMixin
 from .geobodies import GeobodyMixin
+from .intercepts import InterceptMixin
 from .step import Prior, Step
 from .sharding import (EmulatedGroup, allreduce_sum_, assemble_columns, backend_of, exchange_blocks, exchange_blocks_finish,
                        exchange_blocks_start, gather_rows, gather_slices, shard_columns)
@@ -133,7 +134,7 @@ def _on_device(fn):
 
 
 class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixin, SetStatisticsMixin, CrossValidationMixin, BlockSupportMixin,
-                      PointPredictionMixin, ResourceMixin, GeobodyMixin):
+                      PointPredictionMixin, ResourceMixin, GeobodyMixin, InterceptMixin):
     def __init__(self, settings, device=None, rank=0, world=1, group=None, profile=False, method="auto", assembly="f64",
                  operators="resident"):
         """assembly "f32": covariance tables rounded through fp32 and A K kept in fp32 in HBM (BASELINE config 5, "fp32 kernel

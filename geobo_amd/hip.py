@@ -1105,6 +1105,128 @@ def bodies(F, grid, p, thresholds, lo=None, mask=None, weight=None, neighbours=6
     return stats, sums, info
 
 
+TRACE_LMAX = 4096
+TRACE_DETAIL = ("thick", "top", "start", "len", "n_int", "zero")     # columns of detail
+TRACE_DSUM = ("acc", "run_sum")                                       # columns of dsum
+TRACE_TAB = ("holes_hit", "thick", "longest")                         # columns of tab
+TRACE_MAPS = (("hits_any", torch.int32), ("hits", torch.int32), ("thick_sum", torch.int64), ("top_sum", torch.int64), ("acc_sum", F64),
+              ("hist_len", torch.int32), ("hist_thick", torch.int32))
+
+
+def check_traces(offsets, voxels, n):
+    """Host validation of a CSR trace list for geobo_trace_stats (which cannot read the device copies): offsets (K + 1,) ascending from
+    0 with lengths in 1 .. 4096, voxels (offsets[K],) in 0 .. n - 1.  Returns (offsets int32, voxels int32, K, Lmax); ValueError
+    otherwise."""
+    off = np.asarray(offsets)
+    vox = np.asarray(voxels)
+    if off.ndim != 1 or off.size < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError("trace offsets are a 1-D integer array of K + 1 >= 2 entries")
+    if vox.ndim != 1 or not np.issubdtype(vox.dtype, np.integer):
+        raise ValueError("trace voxels are a 1-D integer array")
+    off, vox = off.astype(np.int64), vox.astype(np.int64)
+    if off[0] != 0 or off[-1] != vox.size or vox.size > np.iinfo(np.int32).max:
+        raise ValueError("trace offsets run from 0 to the number of voxels (%d), got %d .. %d" % (vox.size, off[0], off[-1]))
+    length = np.diff(off)
+    if length.min() < 1 or length.max() > TRACE_LMAX:
+        raise ValueError("a trace holds between 1 and %d positions, got %d .. %d" % (TRACE_LMAX, length.min(), length.max()))
+    if vox.min() < 0 or vox.max() >= int(n):
+        raise ValueError("a trace voxel lies outside 0 .. %d" % (int(n) - 1))
+    return np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(vox, dtype=np.int32), int(off.size - 1), int(length.max())
+
+
+class TraceSet:
+    """A validated CSR trace list on the device (built once, used by every launch)."""
+
+    def __init__(self, offsets, voxels, n, device="cuda"):
+        off, vox, self.K, self.Lmax = check_traces(offsets, voxels, n)
+        self.n = int(n)
+        self.lengths = np.diff(off.astype(np.int64))
+        require_gpu()
+        self.offsets = torch.as_tensor(off, device=device)
+        self.voxels = torch.as_tensor(vox, device=device)
+
+
+def trace_stats_ws_doubles(S, K, C):
+    nbytes = _lib.load().geobo_trace_stats_ws_bytes(int(S), int(K), int(C))
+    if nbytes == 0:
+        raise ValueError("trace_stats: invalid samples %r, traces %r or cutoffs %r" % (S, K, C))
+    return nbytes // 8
+
+
+def trace_maps(C, K, Lmax, device="cuda", hist=True):
+    """The zeroed accumulators of trace_stats: dict of hits_any, hits (C, K) int32, thick_sum, top_sum (C, K) int64, acc_sum (C, K)
+    fp64 and with hist hist_len, hist_thick (C, K, Lmax + 1) int32."""
+    out = {}
+    for name, dtype in TRACE_MAPS:
+        if name.startswith("hist"):
+            if hist:
+                out[name] = torch.zeros((C, K, Lmax + 1), dtype=dtype, device=device)
+        else:
+            out[name] = torch.zeros((C, K), dtype=dtype, device=device)
+    return out
+
+
+def trace_stats(F, grid, p, thresholds, lo=None, mask=None, traces=None, min_len=1, max_gap=0, maps=None, detail=None, dsum=None,
+                tab=None, ws=None):
+    """Drill-intercept statistics of S cubes F (S, 3, n) on `grid` = (ny, nx, nz) along traces: `traces` = a TraceSet, or None for
+    the ny nx z-columns.  The ore of (s, c) is the set of cutoff_stats (same thresholds, lo, mask); a run of non-ore positions of at
+    most max_gap samples, all eligible, between two ore positions is filled; the longest run of the result is the BEST intercept
+    and counts as a hit from min_len samples on.  Returns tab (S, C, 3) int64 -- the columns TRACE_TAB.  maps: dict of accumulators
+    (trace_maps; any subset), incremented; detail (S, C, K, 6) int32 -- TRACE_DETAIL -- and dsum (S, C, K, 2) fp64 -- TRACE_DSUM --
+    are written when given.  Exact integers, bitwise reproducible sums, the same for any grouping of samples."""
+    lib = require_gpu()
+    S, n, ss, ps = _samples(F, "F")
+    grid = tuple(int(v) for v in grid)
+    if len(grid) != 3 or n != grid[0] * grid[1] * grid[2]:
+        raise ValueError("F holds %d elements per property, the grid %r does not" % (n, grid))
+    t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    lo_h = np.ascontiguousarray(np.full(3, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1))
+    C_ = t.size
+    if lo_h.size != 3:
+        raise ValueError("lo holds one lower bound per property")
+    dev = F.device
+    if mask is not None:
+        _chk(mask, "mask", torch.uint8)
+        assert mask.is_contiguous() and mask.numel() == n
+    null = C.c_void_p(None)
+    opt = lambda x: null if x is None else _p(x)
+    if traces is None:
+        K, Lmax, off_p, vox_p = grid[0] * grid[1], grid[2], null, null
+    else:
+        if not isinstance(traces, TraceSet) or traces.n != n:
+            raise ValueError("traces is a TraceSet validated for the %d voxels of F" % n)
+        K, Lmax, off_p, vox_p = traces.K, traces.Lmax, _p(traces.offsets), _p(traces.voxels)
+    maps = maps or {}
+    ptr = {}
+    for name, dtype in TRACE_MAPS:
+        m = maps.get(name)
+        if m is not None:
+            _chk(m, name, dtype)                      # (the kernel's uint32 counters travel as int32: torch has no arithmetic on uint32)
+            assert m.is_contiguous() and tuple(m.shape) == ((C_, K, Lmax + 1) if name.startswith("hist") else (C_, K)), name
+        ptr[name] = opt(m)
+    if set(maps) - set(ptr):
+        raise ValueError("unknown maps %r" % sorted(set(maps) - set(ptr)))
+    if detail is not None:
+        _chk(detail, "detail", torch.int32)
+        assert detail.is_contiguous() and tuple(detail.shape) == (S, C_, K, 6)
+    if dsum is not None:
+        _chk(dsum, "dsum")
+        assert dsum.is_contiguous() and tuple(dsum.shape) == (S, C_, K, 2)
+    if tab is None:
+        tab = torch.empty((S, C_, 3), dtype=torch.int64, device=dev)
+    _chk(tab, "tab", torch.int64)
+    assert tab.is_contiguous() and tuple(tab.shape) == (S, C_, 3)
+    need = trace_stats_ws_doubles(S, K, C_)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=F64, device=dev)
+    _lib.check(lib.geobo_trace_stats(S, _p(F), ss, ps, *grid, int(p), C_, t.ctypes.data_as(C.POINTER(C.c_double)),
+                                     lo_h.ctypes.data_as(C.POINTER(C.c_double)), opt(mask), K, off_p, vox_p, Lmax, int(min_len), int(max_gap),
+                                     _p(tab), ptr["hits_any"], ptr["hits"], ptr["thick_sum"], ptr["top_sum"], ptr["acc_sum"],
+                                     ptr["hist_len"], ptr["hist_thick"], opt(detail), opt(dsum), _p(_chk(ws, "ws")), ws.numel() * 8,
+                                     _stream()), "geobo_trace_stats")
+    return tab
+
+
 def mfma_f64_peak(blocks=1024, iters=20000):
     """Time the v_mfma_f64_16x16x4_f64 issue rate; returns TFLOP/s (4 waves/WG x 16 MFMA x 2048 flop per iter)."""
     lib = require_gpu()

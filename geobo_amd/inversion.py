@@ -645,6 +645,144 @@ class Inversion:
         numbered, sizes = gb.renumber(labels.cpu().numpy().reshape(grid))
         return numbered, sizes
 
+    # ---- drill-intercept statistics ------------------------------------------------------------------------
+    def _region_mask(self, region, shape):
+        if region is None:
+            return None
+        region = np.asarray(region)
+        if region.dtype != np.bool_ or region.shape != tuple(shape):
+            raise ValueError("region must be a boolean array of shape %r, got %r %r" % (tuple(shape), region.dtype, region.shape))
+        return torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=self.engine.device)
+
+    def drill_intercepts(self, cutoffs, prop="drill", n=256, seed=0, start=0, batch=64, offset=0.0, require=None, region=None,
+                         min_length=None, max_gap=0.0, holes=None, paths=None, step=None, approximate=False, write=False):
+        """What drill holes would intersect, from the n posterior realisations sample_posterior(n, seed, start) of the last cubing()
+        survey, reduced on the device.  cutoffs, prop, n, seed, start, batch, offset, require, region and approximate are those of
+        grade_tonnage(): the ORE of a realisation and a cutoff is the set that grade_tonnage() counts.  Along a hole, a run of
+        non-ore samples no longer than max_gap that lies inside the region, holds no NaN and has ore immediately before and after it
+        is composited in (internal dilution); the INTERCEPTS are the runs of the result and the BEST one is the longest (a tie goes
+        to the shallower).  min_length and max_gap are metres down the hole and are converted to samples of the down-hole sample
+        length -- zvoxsize for vertical holes, `step` for paths -- by min_len = ceil(min_length / sample length) and
+        max_gap = floor(max_gap / sample length) (a quotient within 1e-9 of an integer counts as it); min_length=None is one sample.
+        Default: every vertical column of the cube.  Returns a dict with the cutoffs in the caller's order:
+          `cutoffs` (C,); per realisation, (n, C): `holes_hit` = the columns whose best intercept reaches min_length,
+          `prospective_area` = holes_hit x xvoxsize x yvoxsize, `longest` = the longest intercept of any column (m), `count` = the ore
+          samples of all columns (grade_tonnage()'s count), `quantiles` = {"prospective_area", "longest"}, each (3, C) at 10 / 50 /
+          90 %; maps (C, yN, xN): `probability` (best intercept >= min_length), `probability_any` (any ore), `thickness` and
+          `intercept_length` = dicts of `mean`, `p10`, `p50`, `p90` in metres (the quantiles are exact, by the inverted CDF of
+          np.quantile(method="inverted_cdf"), from per-column histograms), `depth_to_top_mean` (m below the cube top, given
+          presence; NaN where never present) and `accumulation_mean` = the mean of grade x metres, (scale x sum + offset x count) x
+          sample length.
+        holes = [(ix, iy), ...] (vertical holes at voxel columns) or paths = [(x0, y0, azimuth, dip), ...] (dipping holes in the
+        convention of Acquisition.path_voxels, one sample per `step` at the ranges and with the length convention of predict_path(),
+        steps inside one voxel repeating it): the same summaries per hole, (C, K) instead of (C, yN, xN), without the area, plus
+        `per_realisation` = dict of (n, C, K) arrays: `thickness`, `depth_to_top`, `from`, `length` (m), `grade` = the mean value of
+        the best intercept with its composited waste, `accumulation`, `n_intercepts`; and `trace_lengths` (K,) in samples.
+        Always: `sample_length` (m) and the converted `min_len` and `max_gap_samples`.
+        write=True: intercepts.csv and intercept_maps.csv (columns) or hole_intercepts.csv (holes, paths) in outpath.
+        Block support, several ranks and a campaign utility built on these probabilities are out of scope."""
+        from . import hip, intercepts as ic, resources
+        s = self.settings
+        p = resources.property_index(prop)
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("drill_intercepts() reduces realisations of the survey of cubing(): call cubing() first")
+        scale = [float(v) for v in self._cube_scale]
+        bounds = {resources.property_index(k): float(v) for k, v in (require or {}).items()}
+        if p in bounds:
+            raise ValueError("require names the other properties: %r is the one the cutoffs apply to" % (prop,))
+        if self.drillfield.size == 0 and (p == 2 or 2 in bounds):
+            raise ValueError("the drill cubes are NaN without drill data: no cutoff on them")
+        if holes is not None and paths is not None:
+            raise ValueError("give holes or paths, not both")
+        lo = np.full(3, -np.inf)
+        for q, v in bounds.items():
+            if np.isnan(v):
+                raise ValueError("a lower bound of require is NaN")
+            lo[q] = v / scale[q]
+        cut = np.asarray(cutoffs, dtype=np.float64).reshape(-1)
+        t, order = resources.normalised_thresholds(cut, offset, self._cube_scale[p])
+        grid = (s.yNcube, s.xNcube, s.zNcube)
+        n, start = int(n), int(start)
+        if n < 1 or start < 0:
+            raise ValueError("n >= 1 realisations from start >= 0, got n = %r, start = %r" % (n, start))
+        eng = self.engine
+        if eng.world > 1:
+            raise NotImplementedError("drill intercepts run on one rank (world = %d)" % eng.world)
+        mask = self._region_mask(region, grid)
+        dz, csr = float(s.zvoxsize), None
+        if holes is not None:
+            csr = ic.hole_traces(holes, grid)
+        elif paths is not None:
+            off, vox, dz = ic.path_traces(s, paths, step)
+            csr = (off, vox)
+        min_len, gap = ic.samples_of(min_length, max_gap, dz)
+        traces = None if csr is None else hip.TraceSet(csr[0], csr[1], eng.N, device=eng.device)
+        K, Lmax = (grid[0] * grid[1], grid[2]) if traces is None else (traces.K, traces.Lmax)
+        maps = hip.trace_maps(t.size, K, Lmax, device=eng.device)
+        tabs, dets, dsms = [], [], []
+        for fp, _, _ in self._posterior_batches(n, seed, start, approximate, batch):
+            r = eng.trace_statistics(fp, p, t, lo=lo, mask=mask, traces=traces, min_len=min_len, max_gap=gap, maps=maps,
+                                     detail=traces is not None)
+            if traces is None:
+                tabs.append(r)
+            else:
+                tabs.append(r[0])
+                dets.append(r[1].cpu())
+                dsms.append(r[2].cpu())
+        inv_order = np.empty_like(order)
+        inv_order[order] = np.arange(order.size)
+        out = dict(cutoffs=cut.copy(), sample_length=dz, min_len=min_len, max_gap_samples=gap)
+        out.update(ic.intercept_tables(torch.cat(tabs).cpu().numpy()[:, inv_order], dz,
+                                       float(s.xvoxsize) * float(s.yvoxsize) if traces is None else None))
+        host = {k: v.cpu().numpy()[inv_order] for k, v in maps.items()}
+        summary = ic.intercept_maps(host, n, scale[p], offset, dz)
+        if traces is None:
+            shape = (t.size, grid[0], grid[1])
+            summary = {k: ({q: a.reshape(shape) for q, a in v.items()} if isinstance(v, dict) else v.reshape(shape)) for k, v in summary.items()}
+        out.update(summary)
+        if traces is not None:
+            out["per_realisation"] = ic.per_realisation(torch.cat(dets).numpy()[:, inv_order], torch.cat(dsms).numpy()[:, inv_order], scale[p],
+                                                        offset, dz)
+            out["trace_lengths"] = traces.lengths.copy()
+        if approximate:
+            out["clipped_fraction"] = self._sampler_cache[1].clipped_fraction
+        if write:
+            import os
+            if traces is None:
+                ic.curve_frame(out).to_csv(os.path.join(s.outpath, "intercepts.csv"), index=False)
+                x = (np.arange(s.xNcube) + 0.5) * s.xvoxsize + s.xmin
+                y = (np.arange(s.yNcube) + 0.5) * s.yvoxsize + s.ymin
+                ic.map_frame(out, x, y).to_csv(os.path.join(s.outpath, "intercept_maps.csv"), index=False)
+            else:
+                ic.hole_frame(out).to_csv(os.path.join(s.outpath, "hole_intercepts.csv"), index=False)
+        return out
+
+    def column_intercepts(self, cube, cutoff, min_length=None, max_gap=0.0, region=None):
+        """The deterministic companion of drill_intercepts() for any one (yN, xN, zN) cube -- a mean cube, one realisation -- on the
+        device: per vertical column the material at or above `cutoff` (the cube's own units; NaN is outside, region a boolean cube
+        restricting the voxels), min_length and max_gap in metres as there.  Returns a dict of (yN, xN) maps: `thickness` (m),
+        `depth_to_top` (m below the cube top; NaN without ore), `from` and `length` of the best intercept (m; `from` NaN without
+        one), `mean_value` = its mean with the composited waste (NaN without one), `n_intercepts` (of at least min_length)."""
+        from . import intercepts as ic
+        s = self.settings
+        grid = (s.yNcube, s.xNcube, s.zNcube)
+        cube = np.asarray(cube, dtype=np.float64)
+        if cube.shape != grid:
+            raise ValueError("cube must have the shape %r, got %r" % (grid, cube.shape))
+        cutoff = float(cutoff)
+        if np.isnan(cutoff):
+            raise ValueError("the cutoff is NaN")
+        min_len, gap = ic.samples_of(min_length, max_gap, s.zvoxsize)
+        eng = self.engine
+        mask = self._region_mask(region, grid)
+        F = torch.zeros((1, 3, cube.size), dtype=torch.float64, device=eng.device)
+        F[0, 0] = torch.as_tensor(cube.reshape(-1).copy(), device=eng.device)
+        _, det, dsm = eng.trace_statistics(F, 0, [cutoff], mask=mask, min_len=min_len, max_gap=gap, detail=True)
+        r = ic.per_realisation(det.cpu().numpy(), dsm.cpu().numpy(), 1.0, 0.0, s.zvoxsize)
+        shape = (grid[0], grid[1])
+        return {"thickness": r["thickness"].reshape(shape), "depth_to_top": r["depth_to_top"].reshape(shape), "from": r["from"].reshape(shape),
+                "length": r["length"].reshape(shape), "mean_value": r["grade"].reshape(shape), "n_intercepts": r["n_intercepts"].reshape(shape)}
+
     # ---- drill-hole information gain and greedy campaigns (DESIGN.md section 13) ------------------------------------------------
     def _cubing_done(self, what):
         if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):

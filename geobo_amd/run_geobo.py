@@ -94,7 +94,15 @@ def run(settings, method="auto", bayesopt=True, write=True):
             cubes_p = res.get("probability_seeded", res.get("probability_largest"))
             for k, cube in enumerate(cubes_p if cubes_p is not None else ()):
                 dataio.create_vtkcube(cube, origin, size, fname=os.path.join(s.outpath, "cube_%s_connected_%d.vtk" % (PROPS[property_index(prop)], k)))
-    ncamp = int(getattr(s, "drill_campaign", 0) or 0)     # optional YAML keys drill_campaign (q, default 0) and campaign_utility
+    dri = getattr(s, "drill_intercepts", None)            # optional YAML key drill_intercepts: {cutoffs, property, samples, offset,
+    if dri:                                               # min_length, max_gap} (metres), optionally holes or paths (+ step)
+        from .intercepts import parse_yaml
+        kw, along = parse_yaml(dri)
+        seed = int(getattr(s, "sample_seed", 0) or 0)     # (shared with posterior_samples)
+        out["drill_intercepts"] = inv.drill_intercepts(seed=seed, write=write, **kw)
+        if along:
+            out["drill_intercepts_holes"] = inv.drill_intercepts(seed=seed, write=write, **kw, **along)
+    ncamp = int(getattr(s, "drill_campaign", 0) or 0)    # optional YAML keys drill_campaign (q, default 0) and campaign_utility
     if ncamp > 0:
         out["drill_campaign"] = inv.propose_drill_campaign(ncamp, utility=getattr(s, "campaign_utility", None) or "information", write=write)
     if bayesopt:

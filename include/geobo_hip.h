@@ -48,7 +48,9 @@ extern "C" {
  * geobo_block_cov_ws_bytes).
  * Also additive since 212, version unchanged: the grade-tonnage reductions of gradetonnage.hip (geobo_box_means,
  * geobo_cutoff_stats, geobo_cutoff_stats_ws_bytes).
- * Also additive since 212, version unchanged: the connected bodies of geobodies.hip (geobo_bodies, geobo_bodies_ws_bytes). */
+ * Also additive since 212, version unchanged: the connected bodies of geobodies.hip (geobo_bodies, geobo_bodies_ws_bytes).
+ * Also additive since 212, version unchanged: the drill-intercept statistics of intercepts.hip (geobo_trace_stats,
+ * geobo_trace_stats_ws_bytes). */
 
 #define GEOBO_PAD_M 256 /* row padding of M-like dimensions (observation rows)            */
 #define GEOBO_PAD_N 128 /* padding of voxel-like dimensions (columns / contraction index) */
@@ -752,6 +754,42 @@ int geobo_bodies(int64_t S, const double* F, int64_t sstride, int64_t pstride, i
                  const double* lo, const uint8_t* mask, const int32_t* weight, int neighbours, int64_t min_count, int64_t K,
                  const int32_t* seeds, int64_t* stats, double* sums, uint32_t* hits_largest, uint32_t* hits_seeded, int32_t* labels,
                  int32_t* info, int phases, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- drill-intercept statistics along traces (intercepts.hip) ----------------------------------------------
+ * geobo_trace_stats: the realisations, thresholds, bounds and mask of geobo_cutoff_stats on the (ny, nx, nz) grid (voxel order
+ * (iy, ix, iz), n = ny nx nz, iz = 0 at the top).  A TRACE is an ordered list of voxel indices, shallow to deep, in CSR form: K
+ * traces, offsets[K + 1] and voxels[offsets[K]] (int32, both ON THE DEVICE); trace k has L_k = offsets[k + 1] - offsets[k] positions,
+ * 1 <= L_k <= Lmax <= 4096, and may visit a voxel more than once.  voxels == NULL: the z-columns of the grid, K = ny nx, trace k =
+ * the voxels k nz .. k nz + nz - 1, Lmax = nz, offsets ignored.  The CONTENTS of offsets and voxels (monotone offsets, lengths in
+ * 1 .. Lmax, indices in 0 .. n - 1) are not read by the checks here: the caller validates them on the host copy it builds them
+ * from (geobo_amd.hip.trace_stats does).  The kernel clamps a length to 0 .. Lmax and reads no voxel outside 0 .. n - 1.
+ * For sample s, cutoff c, trace k, position j with voxel v_j and x_j = F[s][p][v_j]:
+ *   eligible e_j: mask[v_j] != 0 and x_j is not NaN;   ore o_j: e_j, x_j >= t[c] and F[s][q][v_j] >= lo[q] for both q != p (the
+ *   predicate of geobo_cutoff_stats; NaN fails);   composite k_j: o_j, or j lies in a maximal run of non-ore positions of length
+ *   <= max_gap, all eligible, with an ore position immediately before and after it (internal dilution; max_gap = 0: the ore);
+ *   thick = sum_j o_j, acc = sum_j o_j x_j, top = the smallest j with o_j (L_k if none);  INTERCEPTS = the maximal runs of k_j,
+ *   BEST the longest (a tie goes to the smaller start): len, start, run_sum = sum over BEST of x_j, the filled waste included
+ *   (0, L_k, 0 without an intercept); n_int = the intercepts of length >= min_len; hit = (len >= min_len).
+ * Outputs (each may be NULL but tab):
+ *   tab[s][c][3] (int64): sum_k hit, sum_k thick, max_k len; exact integer reductions;
+ *   hits_any (uint32, thick > 0), hits (uint32, hit), thick_sum (int64), top_sum (int64, over the samples with thick > 0), acc_sum
+ *     (fp64) [c][k]: accumulated over calls, the caller zeroes them once; one owning lane per entry, no atomics.  acc_sum += acc one
+ *     sample after the other in ascending order, starting from the stored value: cutting the samples into calls changes no bit;
+ *   hist_len, hist_thick [c][k][Lmax + 1] (uint32): += 1 in the bin of BEST len and of thick per sample;
+ *   detail[s][c][k][6] (int32): thick, top, start, len, n_int, 0;   dsum[s][c][k][2] (fp64): acc, run_sum.
+ * The floating-point sums add the 64 positions of a word by a fixed butterfly and the words in ascending order: their order depends
+ * on L_k alone, a sample or cutoff reduced alone gives the bits it gives in a batch; no floating-point atomics.  S == 0 is a no-op.
+ * geobo_trace_stats_ws_bytes: the workspace of a call (4 bytes per (sample, trace, cutoff), a multiple of 16), 0 for invalid
+ * arguments.  Checks before any device access (GEOBO_E_ARG): NULL F, t, lo, tab or ws, S < 0, K < 1, S or K > INT32_MAX, an extent
+ * < 1, n > INT32_MAX, C outside 1..32, p outside 0..2, a NaN in t or lo, t not ascending, strides too small, min_len < 1, max_gap
+ * outside 0..4096, Lmax outside 1..4096, voxels without offsets, without voxels K != ny nx or Lmax != nz, ws_bytes too small, ws not
+ * 16-byte aligned. */
+size_t geobo_trace_stats_ws_bytes(int64_t S, int64_t K, int C);
+int geobo_trace_stats(int64_t S, const double* F, int64_t sstride, int64_t pstride, int ny, int nx, int nz, int p, int C, const double* t,
+                      const double* lo, const uint8_t* mask, int64_t K, const int32_t* offsets, const int32_t* voxels, int Lmax,
+                      int min_len, int max_gap, int64_t* tab, uint32_t* hits_any, uint32_t* hits, int64_t* thick_sum, int64_t* top_sum,
+                      double* acc_sum, uint32_t* hist_len, uint32_t* hist_thick, int32_t* detail, double* dsum, void* ws, size_t ws_bytes,
+                      void* stream);
 
 #ifdef __cplusplus
 }
