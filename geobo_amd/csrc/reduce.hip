@@ -12,6 +12,13 @@
 //   geobo_rowgemv       out[r] = sum_c X[r][c] * v[c]
 //                       a forward operator applied to a model, data = A rho (simcube.py:147-150; the synthetic surveys of bench.py and of
 //                       the tests): one workgroup per row, 16-byte loads, a fixed reduction tree (deterministic).  HBM read bound.
+//   geobo_centro_fill   B[r][c] = B[n-1-r][n-1-c] for r >= r0: the second half of a centrosymmetric block of AkA (inversion.py:96) from its
+//                       first half -- the magnetic block of a row-major lattice survey under a vertical field.  Stream copy.
+//   geobo_mirror_rows   the same point mirror on rows of A K (voxel blocks of nz doubles reversed, z kept): for readers of the rows
+//                       the step did not compute.
+//   geobo_mirror_dev    max |a - mirror(b)| and max |a|, |b| of a lattice operator's stencil table / boundary slabs: the measurement
+//                       that decides whether geobo_centro_fill may stand for the product.  Slot-owned partial maxima + one finishing
+//                       pass, no atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "geobo_hip.h"
@@ -85,7 +92,137 @@ __global__ void __launch_bounds__(256) rowgemv_kernel(int64_t m, int64_t n2, con
   }
 }
 
+// ---- the point mirror of a lattice survey (inversion.py:96 on a centrosymmetric magnetic block) --------------------------------
+// One thread per 16-byte pair of the SOURCE row n-1-r: loaded aligned, swapped in registers, stored at the mirrored columns
+// (one 16-byte store when n is even, two 8-byte vector stores when n is odd: the mirrored pair then starts on an odd column).
+__global__ void __launch_bounds__(256) centro_fill_kernel(double* __restrict__ B, int64_t ld, int64_t n, int64_t r0) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t c = 2 * p;
+  if (c >= n) return;
+  for (int64_t r = r0 + blockIdx.y; r < n; r += gridDim.y) {
+    const double* src = B + (n - 1 - r) * ld;       // 2 r0 >= n: r >= r0 > n-1-r, a source row is never a destination
+    double* dst = B + r * ld;
+    if (c + 1 < n) {
+      const v2d v = *reinterpret_cast<const v2d*>(src + c);
+      if ((n & 1) == 0) {
+        v2d w;
+        w.x = v.y;
+        w.y = v.x;
+        *reinterpret_cast<v2d*>(dst + (n - 2 - c)) = w;
+      } else {
+        dst[n - 2 - c] = v.y;
+        dst[n - 1 - c] = v.x;
+      }
+    } else {
+      dst[0] = src[c];                              // n odd: the last column stands alone
+    }
+  }
+}
+
+// X[r][b][:] = X[m-1-r][nb-1-b][:] for r0 <= r < m: rows as nb blocks of nz doubles (voxel (iy, ix) blocks of a row of A K)
+__global__ void __launch_bounds__(256) mirror_rows_kernel(double* __restrict__ X, int64_t ld, int64_t m, int64_t r0, int64_t nb, int nz2) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;      // 16-byte pair of the destination row
+  if (e >= nb * nz2) return;
+  const int64_t b = e / nz2;
+  const int64_t se = (nb - 1 - b) * nz2 + (e - b * nz2);
+  for (int64_t r = r0 + blockIdx.y; r < m; r += gridDim.y)
+    reinterpret_cast<v2d*>(X + r * ld)[e] = reinterpret_cast<const v2d*>(X + (m - 1 - r) * ld)[se];
+}
+
+// NaN-keeping maximum: a NaN anywhere makes the result NaN (the gate that reads it then says no)
+__device__ __forceinline__ double max_keep_nan(double m, double v) { return (v > m || v != v) ? v : m; }
+
+constexpr int MIRROR_SLOTS_X = 4, MIRROR_SLOTS_Y = 256;           // slot-owned partial maxima: [y][x][2]
+
+__global__ void __launch_bounds__(256) mirror_dev_kernel(const double* __restrict__ a, int64_t lda, const double* __restrict__ b, int64_t ldb,
+                                                         int64_t rows, int nx, int nz2, double* __restrict__ part) {
+  __shared__ double sh[2][4];
+  double dev = 0.0, mx = 0.0;
+  const int pairs = nx * nz2;
+  for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    const v2d* pa = reinterpret_cast<const v2d*>(a + r * lda);
+    const v2d* pb = reinterpret_cast<const v2d*>(b + (rows - 1 - r) * ldb);
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < pairs; e += gridDim.x * 256) {
+      const int x = e / nz2;
+      const v2d u = pa[e], w = pb[(nx - 1 - x) * nz2 + (e - x * nz2)];
+      dev = max_keep_nan(max_keep_nan(dev, __builtin_fabs(u.x - w.x)), __builtin_fabs(u.y - w.y));
+      mx = max_keep_nan(max_keep_nan(mx, __builtin_fabs(u.x)), __builtin_fabs(u.y));
+      mx = max_keep_nan(max_keep_nan(mx, __builtin_fabs(w.x)), __builtin_fabs(w.y));
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    dev = max_keep_nan(dev, __shfl_xor(dev, o));
+    mx = max_keep_nan(mx, __shfl_xor(mx, o));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sh[0][threadIdx.x >> 6] = dev;
+    sh[1][threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const double* s = sh[threadIdx.x];
+    part[2 * ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) + threadIdx.x] = max_keep_nan(max_keep_nan(s[0], s[1]), max_keep_nan(s[2], s[3]));
+  }
+}
+
+// the finishing pass: one workgroup folds the slots in a fixed order
+__global__ void __launch_bounds__(256) mirror_dev_finish_kernel(const double* __restrict__ part, int slots, double* __restrict__ out) {
+  __shared__ double sh[2][4];
+  double dev = 0.0, mx = 0.0;
+  for (int s = threadIdx.x; s < slots; s += 256) {
+    dev = max_keep_nan(dev, part[2 * s]);
+    mx = max_keep_nan(mx, part[2 * s + 1]);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    dev = max_keep_nan(dev, __shfl_xor(dev, o));
+    mx = max_keep_nan(mx, __shfl_xor(mx, o));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sh[0][threadIdx.x >> 6] = dev;
+    sh[1][threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const double* s = sh[threadIdx.x];
+    out[threadIdx.x] = max_keep_nan(max_keep_nan(s[0], s[1]), max_keep_nan(s[2], s[3]));
+  }
+}
+
 }  // namespace
+
+extern "C" int geobo_centro_fill(double* B, int64_t ld, int64_t n, int64_t r0, void* stream) {
+  if (!B || ((uintptr_t)B & 15) || n < 0 || r0 < 0 || r0 > n || 2 * r0 < n || ld < n) return GEOBO_E_ARG;
+  if (ld & 1) return GEOBO_E_ALIGN;
+  if (r0 == n) return GEOBO_OK;
+  const int64_t gy = n - r0 < 65535 ? n - r0 : 65535;
+  hipLaunchKernelGGL(centro_fill_kernel, dim3((unsigned)(((n + 1) / 2 + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, B, ld, n, r0);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
+
+extern "C" int geobo_mirror_rows(double* X, int64_t ld, int64_t m, int64_t r0, int64_t nb, int nz, void* stream) {
+  if (!X || m < 0 || r0 < 0 || r0 > m || 2 * r0 < m || nb <= 0 || nz <= 0 || nb * nz > ld) return GEOBO_E_ARG;
+  if ((nz & 1) || (ld & 1) || ((uintptr_t)X & 15)) return GEOBO_E_ALIGN;
+  if (r0 == m) return GEOBO_OK;
+  const int64_t pairs = nb * (nz / 2), gy = m - r0 < 65535 ? m - r0 : 65535;
+  hipLaunchKernelGGL(mirror_rows_kernel, dim3((unsigned)((pairs + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, X, ld, m, r0, nb,
+                     nz / 2);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
+
+extern "C" size_t geobo_mirror_dev_ws_bytes(void) { return sizeof(double) * 2 * MIRROR_SLOTS_X * MIRROR_SLOTS_Y; }
+
+extern "C" int geobo_mirror_dev(const double* a, int64_t lda, const double* b, int64_t ldb, int64_t rows, int nx, int nz, double* out2, void* ws,
+                                size_t ws_bytes, void* stream) {
+  if (!a || !b || !out2 || !ws || rows <= 0 || nx <= 0 || nz <= 0 || ws_bytes < geobo_mirror_dev_ws_bytes()) return GEOBO_E_ARG;
+  if ((int64_t)nx * nz > lda || (int64_t)nx * nz > ldb || (int64_t)nx * nz >= (1LL << 31)) return GEOBO_E_ARG;
+  if ((nz & 1) || (lda & 1) || (ldb & 1) || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)ws & 15)) return GEOBO_E_ALIGN;
+  const int pairs = nx * (nz / 2);
+  const int gx = (pairs + 255) / 256 < MIRROR_SLOTS_X ? (pairs + 255) / 256 : MIRROR_SLOTS_X;
+  const int gy = rows < MIRROR_SLOTS_Y ? (int)rows : MIRROR_SLOTS_Y;
+  hipLaunchKernelGGL(mirror_dev_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, rows, nx, nz / 2, (double*)ws);
+  hipLaunchKernelGGL(mirror_dev_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, gx * gy, out2);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
 
 extern "C" int geobo_rowgemv(int64_t m, int64_t n, const double* X, int64_t ld, const double* v, double* out, void* stream) {
   if (!X || !v || !out) return GEOBO_E_ARG;

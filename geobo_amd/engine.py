@@ -70,6 +70,18 @@ class FactorisationTimeout(RuntimeError):
     shared with other processes can do that); the result is undefined.  Inversion retries the step once on the stream schedule."""
 
 
+class _LastStep(dict):
+    """engine.last.  `complete` (set by a mirrored step): fills the rows of A K the step did not compute; run on the first read of the
+    buffer ("AK_partial"), never inside the step."""
+    complete = None
+
+    def __getitem__(self, key):
+        if key == "AK_partial" and self.complete is not None:
+            fill, self.complete = self.complete, None
+            fill()
+        return dict.__getitem__(self, key)
+
+
 def create_cov_lengths(gplength):
     """kernels.py:174-180 -- create_cov edits the caller's length array IN PLACE: [l,l,l] -> [l,1.02l,l]."""
     p = np.asarray(gplength)
@@ -192,6 +204,11 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self._lattice_plan = None
         self._gram, self._lam, self._edgeV = None, {}, {}
         self._lamW, self._edgeVt = {}, {}     # transposed lattice application: permuted eigen-data, boundary-slab spectra
+        # Mirrored magnetic block of AkA ("point mirror"): GEOBO_AKA_MIRROR=0 switches it off -- resolved HERE,
+        # once per engine, not in plan.SWITCHES (the planner's pinned route table counts its switches).  aka_mirror[func]: what the last
+        # operator build measured and what the last step did with it -- dict(deviation, bound, symmetric, taken); _mirror: (operator, symmetric)
+        self.aka_mirror_on = os.environ.get("GEOBO_AKA_MIRROR", "1") != "0"
+        self.aka_mirror, self._mirror, self._mirror_meas = {}, {}, None
         # Row form (plan.Route.family "rows", rowform.py): statically possible; whether a step takes it is decided when the operators
         # are built (lattice survey, even stencils).  Column form from 4 ranks: row-sharded transforms + one all-to-all of A K block
         # columns per operator (with 2 ranks the exchange would move a quarter of A K over ONE xGMI link, more than the forward passes
@@ -286,6 +303,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         key = (func, loc.tobytes(), Bkey, partial, stream_it, rows_mode)
         if key in self._A:
             return self._A[key]
+        self._mirror.pop(func, None)        # (measured below where the mirrored block can apply: _mirror_static)
+        self.aka_mirror.pop(func, None)
         rows_r = self.Ms // self.world if rows_mode else 0
         if rows_mode and not stream_it and self.world > 1:
             A = self._workspace2d("Arows_" + func, rows_r, self.N_pad)        # the handle of a row-form operator IS its row shard
@@ -331,7 +350,14 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                 # one two-sensor call leaves the stencil table Q in the lattice workspace (the Gram's eigen-data come from it)
                 tmp = self._workspace2d("op_rows2", 2, self.N_pad)
                 self._timed("a_sens_" + func, 0.0, lambda: A.rows_into(tmp, 0, 2))
-                lam = self._gram_eigen(plan, lws, rows=rows_mode)
+                feed = self.use_spectral and self._spectral_product().forms.lattice_feed and not self.f32
+                mirror = None
+                if feed and self._mirror_static(plan):
+                    # the boundary slabs enter the mirror measurement, which shares the evenness check's host read: kept first
+                    self._timed("a_sens_" + func, 0.0, lambda: A.keep_stencil(func))
+                    mirror = (A.lattice.Q.view(2 * self.ny - 3, 2 * self.nx - 1, self.nz), A.edge[:, :plane], A.edge[:, plane:2 * plane])
+                lam = self._gram_eigen(plan, lws, rows=rows_mode, mirror=mirror)
+                self._mirror_record(func, A, mirror)
                 if lam is None and rows_mode:
                     self._deny_rows(func, (skey, Bkey), "the %s stencil is not even in both lattice offsets" % func)
                     return self.operator(func, sensor_locations, B=B, axes=axes, full=full)
@@ -339,7 +365,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                     # "auto" and the stencil is not even (no lattice Gram): AkA is an N-deep GEMM against the operator -- resident
                     self._auto_denied.add(dkey)
                     return self.operator(func, sensor_locations, B=B, axes=axes, full=full)
-                if self.use_spectral and self._spectral_product().forms.lattice_feed and not self.f32:
+                if feed and A.lattice is None:
                     self._timed("a_sens_" + func, 0.0, lambda: A.keep_stencil(func))
             self._lam[func] = None if lam is None else (A, lam)
             if rows_mode:
@@ -391,7 +417,11 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         else:
             self._timed("a_sens_" + func, 0.0, lambda: hip.a_sens(func, Bv, locd, self.nx, self.ny, self.nz, xed, yed, zed, mul, div, A,
                                                                  plan=plan, ws=lws))
-            lam = self._gram_eigen(plan, lws) if plan is not None else None
+            mirror = None
+            if self._mirror_static(plan):
+                mirror = (hip.a_sens_lattice_stencil(lws, self.nx, self.ny, self.nz), A[:, :plane], A[:, (self.ny - 1) * plane:self.ny * plane])
+            lam = self._gram_eigen(plan, lws, mirror=mirror) if plan is not None else None
+            self._mirror_record(func, A, mirror)
             self._lam[func] = None if lam is None else (A, lam)      # valid for exactly this operator tensor
         self._A = {k: v for k, v in self._A.items() if k[0] != func}  # one operator per type stays resident
         self._edgeV = {k: v for k, v in self._edgeV.items() if k[0] != func}   # (spectra of the previous operator's boundary slabs)
@@ -527,10 +557,10 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
     def clear_operators(self):
         """Drop the resident forward operators (the benchmark rebuilds them inside every timed step)."""
         self._A = {}
-        self._lam = {}
+        self._lam, self._mirror = {}, {}
         self._edgeV, self._edgeVt, self._lamW = {}, {}, {}
         self._rowsrc, self._Aedge, self._Arows = {}, {}, {}
-        self._lattice_plan = None      # host analysis of the survey geometry + its device copies: part of the operator build
+        self._lattice_plan = None     # host analysis of the survey geometry + its device copies: part of the operator build
 
     def release(self):
         """Give the device memory back (workspaces, transform buffers, operators, eigen-data); the engine rebuilds what the next
@@ -657,10 +687,12 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             # here once per operator and step (spectral.plane_pool) -- no forward transform per row
             pooled = (isinstance(A, StreamedOperator) and A.lattice is not None and A.lattice.jy is not None and not self.f32
                       and sp.pool_applies())
-            fl = sp.flops(self.Ms, len(lams), y1 - y0, fwd_planes=sp.pool_planes(self.Ms) if pooled else None)
-            fv = sp.flops_valu(self.Ms, len(lams), y1 - y0)
+            # mirrored magnetic block (step.mirror): only the rows whose AkA rows are computed; the others are never written
+            Mrun = step.mirror if (s_ == 1 and step.mirror) else self.Ms
+            fl = sp.flops(Mrun, len(lams), y1 - y0, fwd_planes=sp.pool_planes(Mrun) if pooled else None)
+            fv = sp.flops_valu(Mrun, len(lams), y1 - y0)
             if not self.f32 and not isinstance(A, StreamedOperator):
-                self._timed("spectral_product", fl, lambda: sp.product(A, self.Ms, lams, outs, y0, y1), valu=fv)
+                self._timed("spectral_product", fl, lambda: sp.product(A, Mrun, lams, [o[:Mrun] for o in outs], y0, y1), valu=fv)
                 continue
 
             def batches():
@@ -669,9 +701,9 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                 Rb = sp.R
                 abuf = self._op_rows_buffer() if isinstance(A, StreamedOperator) else None
                 scr = [self._workspace2d("ak_rows64_%d" % jj, Rb, nc) for jj in range(len(lams))] if self.f32 else None
-                pool = sp.plane_pool(A.lattice, self.Ms, A.lattice.jy, A.lattice.jx) if pooled else None
-                for r0 in range(0, self.Ms, Rb):
-                    R = min(Rb, self.Ms - r0)
+                pool = sp.plane_pool(A.lattice, Mrun, A.lattice.jy, A.lattice.jx) if pooled else None
+                for r0 in range(0, Mrun, Rb):
+                    R = min(Rb, Mrun - r0)
                     if pool is not None:
                         src = pool.rows(r0)                   # no rows and no transform of them: the y stage reads the pool
                     elif abuf is not None and A.lattice is not None:
@@ -694,9 +726,41 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             hit = self._edgeV[key] = (ycols.data_ptr(), self._gram.edge_eigen(ycols))
         return hit[1]
 
-    def _gram_eigen(self, plan, lws, rows=False):
+    MIRROR_BOUND = 2.0 ** -48      # |a - mirror(a)| <= 2^-48 max|a|: a condition on the operator, not a tuning value
+
+    def _mirror_static(self, plan):
+        """What the mirrored magnetic block of AkA needs before anything is measured: the one-rank `single` family, fp64 assembly, a
+        row-major lattice survey with a sensor over every voxel column (sensor r and sensor Ms - 1 - r are point mirrors)."""
+        return bool(self.aka_mirror_on and plan is not None and plan["rowmajor"] and self.route.family == "single" and self.world == 1
+                    and not self.exchange and not self.f32 and self.Ms_pad == self.Ms)
+
+    def _mirror_record(self, func, A, mirror):
+        """The measurement _gram_eigen's host read brought back for operator A (mirror: what was handed to it, None: not measured): the
+        largest deviation of the stencil table and of the boundary slabs from their point mirror against the largest entry."""
+        meas, self._mirror_meas = self._mirror_meas, None
+        if mirror is None or meas is None:
+            return
+        dq, mq, de, me = meas
+        scale = max(mq, me)
+        ok = bool(dq <= self.MIRROR_BOUND * scale and de <= self.MIRROR_BOUND * scale and scale > 0.0)      # (a NaN anywhere: no)
+        self._mirror[func] = (A, ok)
+        self.aka_mirror[func] = dict(deviation=max(dq, de) / scale if scale > 0.0 else float("nan"), bound=self.MIRROR_BOUND,
+                                     table=(dq, mq), slabs=(de, me), symmetric=ok, taken=False)
+
+    def _mirror_rows(self, step, A_m):
+        """Magnetic rows a step of the symmetric plan has to run when the rest of AkA's magnetic block is the point mirror of them:
+        ceil(Ms / 2) rounded up to the spectral product's batch (0: all rows -- the operator did not measure symmetric, or no gate)."""
+        hit = self._mirror.get("magn")
+        if not (self.aka_mirror_on and step.sym and hit is not None and hit[0] is A_m and hit[1] and 1 in step.props):
+            return 0
+        R = self._spectral_product().R
+        return min(self.Ms, ((self.Ms + 1) // 2 + R - 1) // R * R)
+
+    def _gram_eigen(self, plan, lws, rows=False, mirror=None):
         """Eigen-data of the operator's stencil table for the lattice Gram (lattice_gram.py); None -> AkA by the N-deep GEMM.
-        rows: the row form asks (no column-shard arithmetic applies: every rank correlates whole rows)."""
+        rows: the row form asks (no column-shard arithmetic applies: every rank correlates whole rows).
+        mirror: (stencil table, boundary slab iy = 0, slab iy = ny - 1) of the operator -- their deviation from the point mirror is
+        reduced on the device (geobo_mirror_dev) and read with the evenness check: no second synchronisation per operator build."""
         from .lattice_gram import LatticeGram
         plane = self.nx * self.nz
         Ly = (self.c1 - self.c0) // plane
@@ -715,7 +779,20 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                 return None
         if self._gram is None:
             self._gram = LatticeGram(self._spectral_product(), self.device)
-        return self._timed("aka_lattice_eigen", 0.0, lambda: self._gram.eigen(hip.a_sens_lattice_stencil(lws, self.nx, self.ny, self.nz)))
+        if mirror is None:
+            return self._timed("aka_lattice_eigen", 0.0, lambda: self._gram.eigen(hip.a_sens_lattice_stencil(lws, self.nx, self.ny, self.nz)))
+        Q, E0, E1 = mirror
+
+        def measured():
+            nqx, ws = 2 * self.nx - 1, self._workspace("mirror_ws", (hip.mirror_dev_ws_doubles(),))
+            out = self._workspace("mirror_out", (4,))
+            Q2 = Q.view(2 * self.ny - 3, nqx * self.nz)
+            hip.mirror_dev(Q2, Q2, 2 * self.ny - 3, nqx, self.nz, out=out[0:2], ws=ws)
+            hip.mirror_dev(E0, E1, self.Ms, self.nx, self.nz, out=out[2:4], ws=ws)
+            lam = self._gram.eigen(Q, extra=out)
+            self._mirror_meas = tuple(self._gram.extra_host)
+            return lam
+        return self._timed("aka_lattice_eigen", 0.0, measured)
 
     def _assemble_AkA(self, step, AK, A_g, A_m):
         """AkA = A K A3^T (+ the noise variances) into the workspace step.aka_slot, from what _assemble_AK(step, ...) left."""
@@ -878,6 +955,9 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         step = self._step = self._new_step(Prior(kernelfunc, lengths, weight_matrix(crossweights), gp_amp), props, sel_t, gp_sigma,
                                            keep_signal=bool(keep_K), sym=not self.rows_static and self._sym_ok(A_g, A_m))
         M_pad = step.M_pad
+        step.mirror = self._mirror_rows(step, A_m)
+        for f, rec in self.aka_mirror.items():
+            rec["taken"] = bool(f == "magn" and step.mirror)      # (only the magnetic block has a mirrored form; gravity measures "no")
         AK = self._assemble_AK(step, A_g, A_m)
         self.step_route = "rows" if step.rowpath else ("single" if step.sym else "columns")
         t = self._tick("ak_fused", t)
@@ -977,8 +1057,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         # A K is published only when it is whole; the symmetric plan leaves the blocks (magn rows, block 0) and (sensor rows, block 2)
         # unwritten: that buffer goes under AK_partial (the tests' oracle contacts read its assembled blocks); the row form has none
         whole = AK is not None and not step.sym
-        self.last = dict(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props, sel=sel,
-                         ops=(A_g, A_m), step=step)
+        self.last = _LastStep(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props,
+                              sel=sel, ops=(A_g, A_m), step=step)
+        if step.mirror and step.mirror < self.Ms:
+            # a mirrored step left the magnetic rows behind step.mirror unwritten.  Nothing of the engine reads them (AkA was their only
+            # reader); whoever asks for the buffer gets them by the mirrored row copy, once, so that no stale row is ever seen
+            jj, nc, Msp, Mm = props.index(1), self.nc, self.Ms_pad, step.mirror
+            self.last.complete = lambda: hip.mirror_rows(AK[Msp:Msp + self.Ms, jj * nc:jj * nc + self.N], self.Ms, Mm, self.nx * self.ny, self.nz)
         return out
 
     def _derivative_gram(self, A_g, A_m, sel_t, prior, slot):

@@ -202,6 +202,45 @@ def lamdot_z(batch, planes, px, nz, D, lam, out):
     return out
 
 
+def centro_fill(B, n, r0):
+    """B[r, c] = B[n-1-r, n-1-c] for r0 <= r < n (geobo_centro_fill): the second half of a centrosymmetric block from its first half.
+    B: 2-D row-major view with at least n rows and columns."""
+    lib = require_gpu()
+    ld = _rowmajor(B, "B")
+    assert B.shape[0] >= n and B.shape[1] >= n
+    _lib.check(lib.geobo_centro_fill(_p(B), int(ld), int(n), int(r0), _stream()), "geobo_centro_fill")
+    return B
+
+
+def mirror_rows(X, m, r0, nb, nz):
+    """X[r, (b, z)] = X[m-1-r, (nb-1-b, z)] for r0 <= r < m (geobo_mirror_rows): rows of A K under the point mirror of a lattice survey."""
+    lib = require_gpu()
+    ld = _rowmajor(X, "X")
+    assert X.shape[0] >= m and X.shape[1] >= nb * nz
+    _lib.check(lib.geobo_mirror_rows(_p(X), int(ld), int(m), int(r0), int(nb), int(nz), _stream()), "geobo_mirror_rows")
+    return X
+
+
+def mirror_dev_ws_doubles():
+    return require_gpu().geobo_mirror_dev_ws_bytes() // 8
+
+
+def mirror_dev(a, b, rows, nx, nz, out=None, ws=None):
+    """out[0] = max |a[r, (x, z)] - b[rows-1-r, (nx-1-x, z)]|, out[1] = max(|a|, |b|)  (geobo_mirror_dev); a, b: 2-D row-major views
+    of `rows` rows.  Returns the 2-element device tensor (no host read)."""
+    lib = require_gpu()
+    lda, ldb = _rowmajor(a, "a"), _rowmajor(b, "b")
+    assert a.shape[0] >= rows and b.shape[0] >= rows
+    nws = lib.geobo_mirror_dev_ws_bytes() // 8
+    if ws is None:
+        ws = torch.empty(nws, dtype=F64, device=a.device)
+    if out is None:
+        out = torch.empty(2, dtype=F64, device=a.device)
+    _lib.check(lib.geobo_mirror_dev(_p(a), int(lda), _p(b), int(ldb), int(rows), int(nx), int(nz), _p(_chk(out, "out")), _p(_chk(ws, "ws")),
+                                    ws.numel() * 8, _stream()), "geobo_mirror_dev")
+    return out
+
+
 def convert(src, dst):
     """dst[r, c] = src[r, c] across fp64 <-> fp32 (2-D views, unit column stride, even widths and leading dimensions)."""
     lib = require_gpu()

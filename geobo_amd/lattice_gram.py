@@ -291,8 +291,9 @@ class LatticeGram:
         from .plan import lattice_gram_supported
         return lattice_gram_supported(nx, ny, nz)
 
-    def eigen(self, Q, tol=1e-11):
-        """Lambda^T[ky][z][kx] / (Py Px) from the stencil table Q[(2ny-3)][(2nx-1)][nz]; None if Q is not even in both offsets."""
+    def eigen(self, Q, tol=1e-11, extra=None):
+        """Lambda^T[ky][z][kx] / (Py Px) from the stencil table Q[(2ny-3)][(2nx-1)][nz]; None if Q is not even in both offsets.
+        extra: device doubles that ride along in the evenness check's one host read; left in self.extra_host."""
         nx, ny, nz, Px, Py = self.nx, self.ny, self.nz, self.Px, self.Py
         cy, cx = ny - 2, nx - 1                                         # index of offset 0
         sp = self.sp
@@ -305,7 +306,9 @@ class LatticeGram:
             ys = torch.arange(0, ny - 1, device=self.device) * sy + cy
             xs = torch.arange(0, nx, device=self.device) * sx + cx
             dev.append((Q[ys][:, xs] - Qh[:ny - 1]).abs().max())
-        dev = torch.stack(dev).tolist()
+        dev = torch.stack(dev)
+        dev = (dev if extra is None else torch.cat([dev, extra.reshape(-1)])).tolist()
+        dev, self.extra_host = dev[:4], dev[4:]
         if max(dev[1:]) > tol * dev[0]:
             return None
         T = sp.buf("LG_T", ny * Px * nz)

@@ -88,6 +88,7 @@ class Step:
     # decided by the A K assembly
     sym: bool = False           # only the blocks of A K that AkA's lower triangle needs (transposed order on a lattice survey)
     rowpath: bool = False       # the row-sharded form: no A K at all
+    mirror: int = 0             # > 0 (sym only): magnetic rows the assembly runs; the rest of AkA's magnetic block is their point mirror
     # left for the later stages
     gens: dict = field(default_factory=dict)        # Toeplitz generators of the covariance blocks (s, j)
     fullrows: dict = field(default_factory=dict)    # column form with the row exchange: this rank's whole rows of A K

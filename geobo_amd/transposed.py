@@ -46,15 +46,22 @@ class TransposedPosteriorMixin:
                 gram.edge_rows(X[:, iy * pl:], nrows, self._edge_spectrum(("grav", "magn")[sp_], k, edge_cols(sp_, k, iy)), out)
         blk = lambda r0, j: AK[r0:, props.index(j) * nc:(props.index(j) + 1) * nc]
 
+        # step.mirror: A K holds the first rows of the magnetic block only (engine._assemble_AK_spectral); the block is centrosymmetric
+        # (operator measured: engine._mirror_record), so its remaining rows are the point mirror of the computed ones
+        Mm = step.mirror or self.Ms
+
         def run():
             rows_times_AT(blk(0, 0), self.Ms, 0, AkA[0:, 0:Msp])
             rows_times_AT(blk(0, 1), self.Ms, 1, AkA[0:, Msp:2 * Msp])
-            rows_times_AT(blk(Msp, 1), self.Ms, 1, AkA[Msp:, Msp:2 * Msp])
+            rows_times_AT(blk(Msp, 1), Mm, 1, AkA[Msp:, Msp:2 * Msp])
             AkA[Msp:2 * Msp, :Msp] = AkA[:Msp, Msp:2 * Msp].t()
             if Md:
                 rows_times_AT(blk(off_d, 0), Md, 0, AkA[off_d:, 0:Msp])
                 rows_times_AT(blk(off_d, 1), Md, 1, AkA[off_d:, Msp:2 * Msp])
-        self._timed("aka_lattice", gram.flops(3 * self.Ms + 2 * Md, ny), run)
+        self._timed("aka_lattice", gram.flops(2 * self.Ms + Mm + 2 * Md, ny), run)
+        if step.mirror:
+            # (after gram_rows AND edge_rows of the block: the fill copies finished rows; same stream, so it is ordered behind them)
+            self._timed("aka_centro_fill", 0.0, lambda: hip.centro_fill(AkA[Msp:Msp + self.Ms, Msp:Msp + self.Ms], self.Ms, (self.Ms + 1) // 2))
         return self._finish_AkA(step, AkA)
 
     def _zpath_static_ok(self):

@@ -537,6 +537,32 @@ int geobo_sumsq_accum(int64_t rows, int64_t n, const double* a, int64_t lda, con
  * eigen-data as [planes][px][nz].  nz % 16 == 0; D, lam 16-byte aligned. */
 int geobo_lamdot_z(int64_t batch, int planes, int px, int nz, const double* D, const double* lam, double* out, void* stream);
 
+/* Also additive since 212, version unchanged: the point mirror of a row-major lattice survey (geobo_centro_fill, geobo_mirror_rows,
+ * geobo_mirror_dev, geobo_mirror_dev_ws_bytes).
+ *
+ * Second half of a CENTROSYMMETRIC block of AkA = (A K) A^T (inversion.py:96) from its first half:
+ *     B[r][c] = B[n-1-r][n-1-c]   for r0 <= r < n, 0 <= c < n        (B: n x n, leading dimension ld; rows < r0 are only read)
+ * With the sensors of a row-major lattice survey over every voxel column and a vertical ambient field the magnetic operator maps
+ * onto itself under the point reflection of sensors and voxels, so the magnetic block of AkA has this symmetry and only its first
+ * ceil(n/2) rows need the product.  2 r0 >= n, so that no source row is written (GEOBO_E_ARG otherwise; also for a null B, a B
+ * that is not 16-byte aligned and ld < n); ld even (GEOBO_E_ALIGN); n may be odd (the middle row is then a source only).  The
+ * columns n .. ld-1 are not touched.  16-byte loads of the source row, reversed in registers; one read + one write of half the block. */
+int geobo_centro_fill(double* B, int64_t ld, int64_t n, int64_t r0, void* stream);
+/* The same mirror on rows of A_m K_11 (inversion.py:96's left factor), for readers of the rows a mirrored step did not compute:
+ *     X[r][b][z] = X[m-1-r][nb-1-b][z]   for r0 <= r < m, b < nb voxel columns (iy, ix), z < nz
+ * 2 r0 >= m, nb nz <= ld (GEOBO_E_ARG); nz, ld even, X 16-byte aligned (GEOBO_E_ALIGN). */
+int geobo_mirror_rows(double* X, int64_t ld, int64_t m, int64_t r0, int64_t nb, int nz, void* stream);
+/* Whether an operator HAS that symmetry is measured, not assumed:
+ *     out2[0] = max |a[r][x][z] - b[rows-1-r][nx-1-x][z]|,   out2[1] = max(|a|, |b|)   over r < rows, x < nx, z < nz
+ * (a NaN in either makes the result NaN).  a, b: rows of nx nz doubles, lda / ldb apart.  For the stencil table
+ * Q[2ny-3][2nx-1][nz] of geobo_a_sens_lattice a = b = Q (rows = 2ny-3, nx -> 2nx-1): Q[dy][dx] against Q[-dy][-dx]; for the two
+ * 1e6-padded boundary slabs a = slab iy = 0, b = slab iy = ny-1 of every sensor (rows = Ms): sensor r against sensor Ms-1-r.
+ * Every (row, column chunk) slot owns its partial maxima in ws (geobo_mirror_dev_ws_bytes()), one finishing workgroup folds them:
+ * no atomics, deterministic.  nz, lda, ldb even, a, b, ws 16-byte aligned (GEOBO_E_ALIGN); nx nz <= lda, ldb (GEOBO_E_ARG). */
+size_t geobo_mirror_dev_ws_bytes(void);
+int geobo_mirror_dev(const double* a, int64_t lda, const double* b, int64_t ldb, int64_t rows, int nx, int nz, double* out2, void* ws,
+                     size_t ws_bytes, void* stream);
+
 /* Posterior mean/variance without storing V = L^-1 (A K)   (inversion.py:114-117 + :238's np.diag):
  *     V = Linv * AK (tile by tile, MFMA),  mu[c] = sum_m V[m,c] u[m],  var[c] = prior_var - sum_m V[m,c]^2
  * AK: (m x ncols, ldak); u: m; ws: geobo_posterior_ws_bytes(m, ncols). m % 256 == 0, ncols % 128 == 0.
