@@ -29,6 +29,7 @@ SIGNATURES = {
     "geobo_sumsq_accum": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _int, _dp, _i64, _dp]),
     "geobo_lamdot_z": (_int, [_i64, _int, _int, _int, _dp, _dp, _dp, _dp]),
     "geobo_centro_fill": (_int, [_dp, _i64, _i64, _i64, _dp]),
+    "geobo_transpose": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _dp]),
     "geobo_mirror_rows": (_int, [_dp, _i64, _i64, _i64, _i64, _int, _dp]),
     "geobo_mirror_dev_ws_bytes": (_sz, []),
     "geobo_mirror_dev": (_int, [_dp, _i64, _dp, _i64, _i64, _int, _int, _dp, _dp, _sz, _dp]),

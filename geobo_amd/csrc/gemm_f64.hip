@@ -46,7 +46,10 @@ __device__ __forceinline__ int swz(int row) {
   return (p & 1) | (((p >> 2) & 1) * 6);
 }
 
-enum { Y_GEN = 0, Y_NT = 1, Y_NN = 2, Y_TAB = 3 };
+// Y_NT_XT: Y as in Y_NT, X given TRANSPOSED (k x m, m-contiguous) and staged like the Y_NN operand -- lets a product whose left
+// factor was written by an earlier GEMM as [k][rows] store its result row-major without a transposing pass in between.
+enum { Y_GEN = 0, Y_NT = 1, Y_NN = 2, Y_TAB = 3, Y_NT_XT = 4 };
+constexpr bool mem_mode(int y) { return y == Y_NT || y == Y_NN || y == Y_NT_XT; }
 enum { EPI_STORE = 0, EPI_REDUCE = 1 };
 enum { TRI_LOWER_ONLY = 1, TRI_X_LOWER = 2, TRI_Y_LOWER = 4 };
 
@@ -123,18 +126,23 @@ __host__ __device__ __forceinline__ void tile_of_item(int t, int nbi, int nbj, i
 template <int WM, int WN>
 constexpr int ring_depth() { return (WM * WN >= 8) ? NST : 2; }
 
+// LDS images of one chunk.  [rows][16] tiles (X, Y_NT): XS doubles per row.  [16 k][cols] tiles (Y_NN, the X of Y_NT_XT): one
+// k-row per LDS-DMA wave instruction, row stride cols + 4.
 template <int WM, int WN, int YMODE>
 constexpr int lds_doubles() {
   constexpr int TM = 64 * WM, TN = 64 * WN;
+  constexpr int xbuf = (YMODE == Y_NT_XT) ? BK * (TM + 4) : TM * XS;
   constexpr int ybuf = (YMODE == Y_NN) ? BK * (TN + 4) : TN * XS;
-  return ring_depth<WM, WN>() * (TM * XS + ybuf);
+  return ring_depth<WM, WN>() * (xbuf + ybuf);
 }
 
 template <int WM, int WN, int YMODE, int EPI, int KID>
 __global__ void __launch_bounds__(64 * WM * WN, 2) gemm_f64_kernel(const GemmArgs a) {
   constexpr int TM = 64 * WM, TN = 64 * WN, NT = 64 * WM * WN;
-  constexpr int YS_NN = TN + 4;
-  constexpr int XBUF = TM * XS;
+  constexpr bool XT = (YMODE == Y_NT_XT), YNT = (YMODE == Y_NT || XT);
+  static_assert(!XT || TM == 128, "transposed X: 128-row tiles");
+  constexpr int YS_NN = TN + 4, XS_T = TM + 4;
+  constexpr int XBUF = XT ? BK * XS_T : TM * XS;
   constexpr int YBUF = (YMODE == Y_NN) ? BK * YS_NN : TN * XS;
   constexpr int XU = TM * 8 / NT;                                    // 16-byte units of X per thread per chunk
   constexpr int YU = (YMODE == Y_NN) ? (8 * TN / NT) : (TN * 8 / NT);  // same for Y (memory / lattice modes)
@@ -215,7 +223,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) gemm_f64_kernel(const GemmArg
   // accumulators START as (beta / alpha) C -- exact -- so the loads of C fly together with the first operand chunks instead of
   // sitting, latency exposed, between the last MFMA and the stores (K = 128 update at m = 8192: 378 -> 2xx us).
   bool c_in_acc = false;
-  if constexpr (EPI == EPI_STORE && (YMODE == Y_NT || YMODE == Y_NN)) {
+  if constexpr (EPI == EPI_STORE && mem_mode(YMODE)) {
     c_in_acc = a.beta != 0.0 && (a.beta == a.alpha || a.beta == -a.alpha);
     if (c_in_acc) {
       const double sgn = (a.beta == a.alpha) ? 1.0 : -1.0;
@@ -256,14 +264,22 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) gemm_f64_kernel(const GemmArg
     xsrc[i] = (grow * a.ldx + 2 * ((tid & 7) ^ swz(row))) * 8;
   }
   auto stage_x = [&](int64_t k0, int st) {
+    if constexpr (XT) {
+      // [16 k-rows][TM = 128] tile: one wave instruction = one 1-KiB k-row, as for the Y_NN operand
+#pragma unroll
+      for (int i = 0; i < BK * 64 / NT; ++i) {
+        const int kr = i * (NT / 64) + wave;
+        dma16(Xp + (k0 + kr) * a.ldx + row0 + 2 * lane, Xs + st * XBUF + kr * XS_T);
+      }
+    } else
 #pragma unroll
     for (int i = 0; i < XU; ++i) dma16(Xgb + xsrc[i] + k0 * 8, Xs + st * XBUF + (i * RPI + wave * 8) * XS);
   };
 
   // Y operand, memory modes
-  int64_t ysrc[(YMODE == Y_NT) ? YU : 1];
-  const char* const Ygb = (YMODE == Y_NT) ? reinterpret_cast<const char*>(Yp + col0 * a.ldy) : nullptr;
-  if constexpr (YMODE == Y_NT) {
+  int64_t ysrc[YNT ? YU : 1];
+  const char* const Ygb = YNT ? reinterpret_cast<const char*>(Yp + col0 * a.ldy) : nullptr;
+  if constexpr (YNT) {
 #pragma unroll
     for (int i = 0; i < YU; ++i) {
       const int row = i * RPI + srow;
@@ -305,7 +321,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) gemm_f64_kernel(const GemmArg
   }
 
   auto stage_y = [&](int64_t k0, int st) {
-    if constexpr (YMODE == Y_NT) {
+    if constexpr (YNT) {
 #pragma unroll
       for (int i = 0; i < YU; ++i) dma16(Ygb + ysrc[i] + k0 * 8, Ys + st * YBUF + (i * RPI + wave * 8) * XS);
     } else if constexpr (YMODE == Y_NN) {
@@ -374,12 +390,18 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) gemm_f64_kernel(const GemmArg
   // the fp64 MFMA pipe, which is why the lattice-table mode is the production path on regular grids.
   if (kb < ke) {
     const int xoff0 = 2 * ((2 * lg + 0) ^ swz(lr)), xoff1 = 2 * ((2 * lg + 1) ^ swz(lr));
-    const double* const xfrag = Xs + (wm * 64 + lr) * XS;
+    const double* const xfrag = XT ? (Xs + wm * 64 + lr) : (Xs + (wm * 64 + lr) * XS);
     const double* const yfrag = (YMODE == Y_NN) ? (Ys + wn * 64 + lr) : (Ys + (wn * 64 + lr) * XS);
     auto read_half = [&](int stage, int h, v2d (&av)[4], v2d (&bv)[4]) {
-      const double* xb = xfrag + stage * XBUF + (h ? xoff1 : xoff0);
+      if constexpr (XT) {
+        const double* xb = xfrag + stage * XBUF + (4 * lg + 2 * h) * XS_T;
 #pragma unroll
-      for (int m = 0; m < 4; ++m) av[m] = *reinterpret_cast<const v2d*>(xb + m * 16 * XS);
+        for (int m = 0; m < 4; ++m) { av[m][0] = xb[m * 16]; av[m][1] = xb[XS_T + m * 16]; }
+      } else {
+        const double* xb = xfrag + stage * XBUF + (h ? xoff1 : xoff0);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) av[m] = *reinterpret_cast<const v2d*>(xb + m * 16 * XS);
+      }
       if constexpr (YMODE == Y_NN) {
         const double* yb = yfrag + stage * YBUF + (4 * lg + 2 * h) * YS_NN;
 #pragma unroll
@@ -662,13 +684,13 @@ int launch(GemmArgs& a, hipStream_t st) {
   a.xcd_map = (a.nbi >= 8) ? 1 : 0;
   // supertiles help when both operands stream (measured: posterior_reduce 59 -> 66 TF/s); with lower_only skipping they
   // unbalance the tail (AkA 420 -> 499 ms), so triangular-output launches keep the row-per-XCD map
-  if ((YMODE == Y_NT || YMODE == Y_NN) && !(a.tri & TRI_LOWER_ONLY) && a.nbi >= 4 && a.nbj >= 8) a.xcd_map = 2;
+  if (mem_mode(YMODE) && !(a.tri & TRI_LOWER_ONLY) && a.nbi >= 4 && a.nbj >= 8) a.xcd_map = 2;
   a.ntiles = 0;
   if (a.batch <= 0) a.batch = 1;
   const int64_t items = (int64_t)a.nbi * a.nbj * a.batch;
   // up to a few dozen tiles per CU: the tail of the launch matters -> balanced item list (plain and lower_only NT/NN)
   // (also the triangular-operand merges of the L^-1 build: longest contraction ranges first, equal lengths together)
-  if ((YMODE == Y_NT || YMODE == Y_NN) && EPI == EPI_STORE && a.batch <= 64 &&
+  if (mem_mode(YMODE) && EPI == EPI_STORE && a.batch <= 64 &&
       a.nbi * a.nbj >= ((a.tri & (TRI_X_LOWER | TRI_Y_LOWER)) ? 16 : 64) && items <= 65536 && a.nbi <= 4096 &&
       (a.tri & (TRI_X_LOWER | TRI_Y_LOWER)) != (TRI_X_LOWER | TRI_Y_LOWER)) {
     a.ntiles = (int)tile_items(a.nbi, a.nbj, 64 * WM, 64 * WN, a.tri);
@@ -824,8 +846,17 @@ extern "C" int geobo_gemm_batched(int y_is_kn, int64_t m, int64_t n, int64_t k, 
   a.X = X; a.ldx = ldx; a.Y = Y; a.ldy = ldy; a.C = C; a.ldc = ldc; a.k = k;
   a.alpha = alpha; a.beta = beta; a.tri = 0;
   a.sXb = strideX; a.sYb = strideY; a.sCb = strideC; a.m_valid = m_valid; a.n_valid = n_valid; a.batch = batch;
-  if (y_is_kn) return launch_by_rows<Y_NN, EPI_STORE, COV_D2>(a, m, n, (hipStream_t)stream);
-  return launch_by_rows<Y_NT, EPI_STORE, COV_D2>(a, m, n, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (y_is_kn & ~(1 | GEOBO_GEMM_X_KM)) return GEOBO_E_ARG;
+  if (y_is_kn & GEOBO_GEMM_X_KM) {
+    // the transposed X operand is staged a 128-row k-row at a time: 128 x 128 tiles only
+    if (y_is_kn & 1) return GEOBO_E_UNSUPPORTED;
+    if (m <= 0 || n <= 0 || m % 128 || n % 128) return GEOBO_E_ALIGN;
+    a.nbi = (int)(m / 128); a.nbj = (int)(n / 128);
+    return launch<2, 2, Y_NT_XT, EPI_STORE, COV_D2>(a, st);
+  }
+  if (y_is_kn) return launch_by_rows<Y_NN, EPI_STORE, COV_D2>(a, m, n, st);
+  return launch_by_rows<Y_NT, EPI_STORE, COV_D2>(a, m, n, st);
 }
 
 extern "C" size_t geobo_posterior_ws_bytes(int64_t m, int64_t ncols) {

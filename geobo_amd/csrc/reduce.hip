@@ -14,6 +14,7 @@
 //                       the tests): one workgroup per row, 16-byte loads, a fixed reduction tree (deterministic).  HBM read bound.
 //   geobo_centro_fill   B[r][c] = B[n-1-r][n-1-c] for r >= r0: the second half of a centrosymmetric block of AkA (inversion.py:96) from its
 //                       first half -- the magnetic block of a row-major lattice survey under a vertical field.  Stream copy.
+//   geobo_transpose     dst = src^T, tiled through LDS: the lower-left block of AkA from the upper-right one the lattice Gram computed.
 //   geobo_mirror_rows   the same point mirror on rows of A K (voxel blocks of nz doubles reversed, z kept): for readers of the rows
 //                       the step did not compute.
 //   geobo_mirror_dev    max |a - mirror(b)| and max |a|, |b| of a lattice operator's stencil table / boundary slabs: the measurement
@@ -188,7 +189,31 @@ __global__ void __launch_bounds__(256) mirror_dev_finish_kernel(const double* __
   }
 }
 
+// dst[c][r] = src[r][c]: one 64 x 64 tile per workgroup through LDS (row stride 65: the transposed reads are conflict free), 512-byte
+// runs on both sides
+__global__ void __launch_bounds__(256) transpose_kernel(int64_t rows, int64_t cols, const double* __restrict__ src, int64_t lds,
+                                                        double* __restrict__ dst, int64_t ldd) {
+  __shared__ double t[64][65];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t r0 = (int64_t)blockIdx.y * 64, c0 = (int64_t)blockIdx.x * 64;
+#pragma unroll 4
+  for (int i = ty; i < 64; i += 4)
+    if (r0 + i < rows && c0 + tx < cols) t[i][tx] = src[(r0 + i) * lds + c0 + tx];
+  __syncthreads();
+#pragma unroll 4
+  for (int i = ty; i < 64; i += 4)
+    if (c0 + i < cols && r0 + tx < rows) dst[(c0 + i) * ldd + r0 + tx] = t[tx][i];
+}
+
 }  // namespace
+
+extern "C" int geobo_transpose(int64_t rows, int64_t cols, const double* src, int64_t lds, double* dst, int64_t ldd, void* stream) {
+  if (!src || !dst || rows < 0 || cols < 0 || lds < cols || ldd < rows || (rows + 63) / 64 > 65535) return GEOBO_E_ARG;
+  if (rows == 0 || cols == 0) return GEOBO_OK;
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((cols + 63) / 64), (unsigned)((rows + 63) / 64)), dim3(256), 0, (hipStream_t)stream,
+                     rows, cols, src, lds, dst, ldd);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
 
 extern "C" int geobo_centro_fill(double* B, int64_t ld, int64_t n, int64_t r0, void* stream) {
   if (!B || ((uintptr_t)B & 15) || n < 0 || r0 < 0 || r0 > n || 2 * r0 < n || ld < n) return GEOBO_E_ARG;

@@ -212,6 +212,16 @@ def centro_fill(B, n, r0):
     return B
 
 
+def transpose(src, dst):
+    """dst[c, r] = src[r, c] (geobo_transpose); src, dst: 2-D row-major views that do not overlap, dst at least src's shape transposed."""
+    lib = require_gpu()
+    lds, ldd = _rowmajor(src, "src"), _rowmajor(dst, "dst")
+    rows, cols = src.shape
+    assert dst.shape[0] >= cols and dst.shape[1] >= rows
+    _lib.check(lib.geobo_transpose(int(rows), int(cols), _p(src), int(lds), _p(dst), int(ldd), _stream()), "geobo_transpose")
+    return dst
+
+
 def mirror_rows(X, m, r0, nb, nz):
     """X[r, (b, z)] = X[m-1-r, (nb-1-b, z)] for r0 <= r < m (geobo_mirror_rows): rows of A K under the point mirror of a lattice survey."""
     lib = require_gpu()
@@ -484,20 +494,24 @@ def gemm_fold(y_is_kn, inverse, m, n, k, X, ldx, strideX, Y, ldy, strideY, C_, l
     return C_
 
 
+X_KM = 2          # GEOBO_GEMM_X_KM
+
+
 def gemm_batched(y_is_kn, m, n, k, X, ldx, strideX, Y, ldy, strideY, C_, ldc, strideC, m_valid, n_valid, batch, alpha=1.0,
-                 beta=0.0):
+                 beta=0.0, x_km=False):
     """Raw batched GEMM (see include/geobo_hip.h); X/Y/C are tensors whose data_ptr is the batch-0 origin.
     m, n are COMPUTE extents (multiples of 128: the MFMA tiles run without edge predication on their loads; only the stores look at
     m_valid / n_valid), so operand tiles may overhang the valid rows -- by contract into slack of the same allocation.  That contract
     is checked here (round 5: a per-slot operand of the boundary-slab convolution overhung its tensor by 64 KB at nz = 16, which only
-    aborted once an unmapped page happened to follow it)."""
+    aborted once an unmapped page happened to follow it).  x_km: X is given transposed (k x m, m-contiguous; y_is_kn False only)."""
     lib = require_gpu()
     done = 0
     esz = 8
-    _check_extents("geobo_gemm_batched", ((X, ldx, strideX, m, k, "X"), (Y, ldy, strideY, k if y_is_kn else n, n if y_is_kn else k, "Y")), batch)
+    _check_extents("geobo_gemm_batched", ((X, ldx, strideX, k if x_km else m, m if x_km else k, "X"),
+                                          (Y, ldy, strideY, k if y_is_kn else n, n if y_is_kn else k, "Y")), batch)
     while done < batch:                      # gridDim.y limit
         nb = min(batch - done, 65535)
-        _lib.check(lib.geobo_gemm_batched(1 if y_is_kn else 0, int(m), int(n), int(k), float(alpha),
+        _lib.check(lib.geobo_gemm_batched((1 if y_is_kn else 0) | (X_KM if x_km else 0), int(m), int(n), int(k), float(alpha),
                                           C.c_void_p(X.data_ptr() + done * strideX * esz), int(ldx), int(strideX),
                                           C.c_void_p(Y.data_ptr() + done * strideY * esz), int(ldy), int(strideY), float(beta),
                                           C.c_void_p(C_.data_ptr() + done * strideC * esz), int(ldc), int(strideC),

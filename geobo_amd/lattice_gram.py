@@ -112,7 +112,8 @@ class LatticeGram:
     def edge_rows(self, X, nrows, V, out):
         """out[r, :ny*nx] += X[r, :nx*nz] . E^T for r < nrows, E given by its spectrum V (edge_eigen).  X: view starting at the slab's
         first column (unit column stride, even row stride); the compute extent of the first GEMM overhangs the plane by up to
-        pad128(nz) doubles (inside the next slab / the next row everywhere but at the end of the buffer: staged there)."""
+        pad128(nz) doubles (inside the next slab / the next row everywhere but at the end of the buffer: staged there).  The last GEMM
+        takes its left factor transposed, as the second one wrote it, and accumulates straight into out's row segments."""
         nx, ny, nz, sp, J = self.nx, self.ny, self.nz, self.sp, self.J
         pl, RB = nx * nz, self.EDGE_ROWS
         F2, FiT = self._edge_consts()
@@ -130,9 +131,8 @@ class LatticeGram:
             hip.gemm_batched(True, hip.pad_n(2 * nx), nzp, nx, F2, nx, 0, X[r0:], nz, X.stride(0), Xh, nz, 2 * nx * nz, 2 * nx, nz, R)
             o2 = sp.buf("LG_EO2", nx * 2 * max(J, nz) * RB)                          # [slot][(C | S, jy)][row]
             hip.gemm_batched(False, 2 * J, Rp, 2 * nz, V, 2 * nz, 2 * J * 2 * nz, Xh, 2 * nx * nz, 2 * nz, o2, Rp, 2 * J * Rp, 2 * J, R, nx)
-            oT = sp.buf("LG_EOT", max(J, nz) * nx * RB)                              # [jy][jx][row]
-            hip.gemm_batched(True, nxp, Rp, 2 * nx, FiT, 2 * nx, 0, o2, J * Rp, Rp, oT, Rp, nx * Rp, nx, R, ny)
-            out[r0:r0 + R, :ny * nx] += oT[:ny * nx * Rp].view(ny * nx, Rp)[:, :R].t()
+            # out[row][jy, jx] += sum_(slot, cs) o2[(slot, cs)][jy][row] FiT[jx][(slot, cs)], one product per jy
+            hip.gemm_batched(False, Rp, nxp, 2 * nx, o2, J * Rp, Rp, FiT, 2 * nx, 0, out[r0:], out.stride(0), nx, R, nx, ny, beta=1.0, x_km=True)
 
     # ---- the TRANSPOSED application: rows of L^-1 (one operator's columns) -> rows of L^-1 A  ---------------------------------------
     # Z[r][iy, ix, iz] = sum_(jy, jx) l_r[jy, jx] A[(jy, jx), (iy, ix, iz)]:  on the interior slabs a (y, x) convolution of the row's
@@ -254,7 +254,8 @@ class LatticeGram:
         nx, ny, nz, sp, J = self.nx, self.ny, self.nz, self.sp, self.J
         RB = self.EDGE_ROWS
         F2, FiT = self._edge_consts()
-        nyp, nxp = hip.pad_n(ny), hip.pad_n(nx)
+        nyp, nxp, nzp = hip.pad_n(ny), hip.pad_n(nx), hip.pad_n(nz)
+        assert Lrows.stride(1) == 1 and Lrows.stride(0) % 2 == 0 and out.stride(1) == 1
         end = Lrows.storage_offset() + (nrows - 1) * Lrows.stride(0) + nyp * nx
         if end > Lrows.untyped_storage().nbytes() // 8:                               # compute extents of the first GEMM overhang the row
             Lc = sp.buf("LG_EX", nrows * ny * nx + nyp * nx)[:nrows * ny * nx].view(nrows, ny * nx)
@@ -267,15 +268,18 @@ class LatticeGram:
             if ny < J:
                 Lh.zero_()                                                            # (jy slots >= ny meet zero columns of Vt: keep them finite)
             hip.gemm_batched(False, hip.pad_n(2 * nx), nyp, nx, F2, nx, 0, Lrows[r0:], nx, Lrows.stride(0), Lh, J, 2 * nx * J, 2 * nx, ny, R)
-            o2 = sp.buf("LG_EO2", nx * 2 * max(J, nz) * RB)                           # [slot][(C | S, iz)][row]
-            hip.gemm_batched(False, hip.pad_n(2 * nz), Rp, 2 * J, Vt, 2 * J, 2 * nz * 2 * J, Lh, 2 * nx * J, 2 * J, o2, Rp, 2 * nz * Rp, 2 * nz, R, nx)
-            oT = sp.buf("LG_EOT", max(J, nz) * nx * RB)                               # [iz][ix][row]
-            hip.gemm_batched(True, nxp, Rp, 2 * nx, FiT, 2 * nx, 0, o2, nz * Rp, Rp, oT, Rp, nx * Rp, nx, R, nz)
-            res = oT[:nz * nx * Rp].view(nz, nx, Rp)[:, :, :R]
+            o2 = sp.buf("LG_EO2", nx * 2 * max(J, nz) * RB)
+            # The last product stores straight into the slab, whichever way it is laid out.
             if zx:
-                out[r0:r0 + R, :nx * nz].view(R, nz, nx).copy_(res.permute(2, 0, 1))
+                # o2 [slot][(C | S, iz)][row];  out[row][iz, ix] = sum_(slot, cs) o2[(slot, cs)][iz][row] FiT[ix][(slot, cs)]: one product
+                # per iz, its left factor taken transposed
+                hip.gemm_batched(False, hip.pad_n(2 * nz), Rp, 2 * J, Vt, 2 * J, 2 * nz * 2 * J, Lh, 2 * nx * J, 2 * J, o2, Rp, 2 * nz * Rp, 2 * nz, R, nx)
+                hip.gemm_batched(False, Rp, nxp, 2 * nx, o2, nz * Rp, Rp, FiT, 2 * nx, 0, out[r0:], out.stride(0), nx, R, nx, nz, x_km=True)
             else:
-                out[r0:r0 + R, :nx * nz].view(R, nx, nz).copy_(res.permute(2, 1, 0))
+                # o2 [row][(slot, cs)][iz] (the operands of the second product trade places);  out[row][ix, iz] = FiT o2[row]: one
+                # product per row
+                hip.gemm_batched(False, Rp, hip.pad_n(2 * nz), 2 * J, Lh, 2 * nx * J, 2 * J, Vt, 2 * J, 2 * nz * 2 * J, o2, 2 * nx * nz, 2 * nz, R, 2 * nz, nx)
+                hip.gemm_batched(True, nxp, nzp, 2 * nx, FiT, 2 * nx, 0, o2, nz, 2 * nx * nz, out[r0:], nz, out.stride(0), nx, nz, R)
 
     @staticmethod
     def fast(nx, ny, nz):

@@ -577,15 +577,19 @@ class SpectralProduct:
         """Partial cubes per property block that reduce_ss adds to (sum over them afterwards)."""
         return hip.xz2d_fold_inv_ss_slots(self.nx, self.R, self.ny) if self.fused_ss() else self.GENERIC_SS_SLOTS
 
-    def y2s_tables(self, gens_g, gens_m, pair=(0, 1)):
+    def y2s_tables(self, gens_g, gens_m, pair=(0, 1), check=True):
         """Tables of the three-product form of the two-term rows for the block pair (a, b) = `pair` (b = a + 1, a even), or None where
         the kernel does not apply.  The caller states that gens_g[b] and gens_m[a] are the SAME covariance block -- K_01 = K_10:
         create_cov's prior is symmetric (kernels.py:181-195) -- and the statement is verified on the device: `sym_residual`
         (max |gens_g[b] - gens_m[a]| over max |gens_g[b]|, a 0-d device tensor) is left for the caller to read at its next
-        synchronisation (engine.posterior raises above 1e-12).  Returns (a, D0 = gens_g[a] - X, X = gens_g[b], D1 = gens_m[b] - X)."""
-        self.sym_residual = None
+        synchronisation (engine.posterior raises above 1e-12).  Returns (a, D0 = gens_g[a] - X, X = gens_g[b], D1 = gens_m[b] - X).
+        check=False: tables only, for a second reader of blocks this step has already verified; `sym_residual` is left as it is."""
         a, b = pair
-        if not (self.forms.y2s and b == a + 1 and a % 2 == 0 and b < len(gens_g)):
+        applies = self.forms.y2s and b == a + 1 and a % 2 == 0 and b < len(gens_g)
+        if not check:
+            return (a, gens_g[a] - gens_g[b], gens_g[b], gens_m[b] - gens_g[b]) if applies else None
+        self.sym_residual = None
+        if not applies:
             return None
         x = gens_g[b]
         # (cross weight 0 -- gp_coeff = [.., .., 0], a legal prior -- makes both cross blocks exactly zero: 0 / 0 must not read as
@@ -676,6 +680,41 @@ class SpectralProduct:
                 for i, jj in enumerate(js):
                     hip.xz2d_fold_inv_ss(nx, Rb, ny, sg[i], ny * Cp, Cp, self.F["x"], self.F["z"], ss[jj],
                                          src2=sm[i] if sm is not None else None, in2_row=ny * Cp, r2_first=0)
+
+    def has_two_term_product(self, nblocks):
+        """Whether the y stage of this grid joins the two terms of a row for `nblocks` property blocks (product_two_term): the
+        one-pass kernels take the blocks in pairs, the accumulating form takes any number."""
+        meet = self.forms.y_two_term
+        return self.dense_y and ((meet == "y2t" and nblocks % 2 == 0) or meet == "add")
+
+    def product_two_term(self, Zg, Zm, rows, gens_g, gens_m, outs, y2s=None):
+        """outs[j][r, :] = Zg[r] * K_0j + Zm[r] * K_1j for r < rows <= R: the storing counterpart of reduce_ss's two-term rows.  The
+        terms meet in the y stage (one pass for a pair of blocks -- with y2s tables three products per mode --, or the second term
+        accumulating into the first one's spectrum), ONE storing inverse transform per block.  Grids: has_two_term_product."""
+        ny, C, Cp = self.ny, self.Px * self.Pz, self.Cp
+        P_c, meet = len(gens_g), self.forms.y_two_term
+        assert self.has_two_term_product(P_c) and rows <= self.R
+        t2g = self.forward_zx(Zg, rows, self.G, src_row_stride=Zg.stride(0), out_name="T2")
+        t2m = self.forward_zx(Zm, rows, self.G, src_row_stride=Zm.stride(0), out_name="T2b")
+        for j in range(0, P_c, 2 if meet == "y2t" else 3):
+            js = list(range(j, min(j + (2 if meet == "y2t" else 3), P_c)))
+            u2 = [self.buf(("S", "S1", "S2")[i], rows * ny * Cp) for i in range(len(js))]
+            gg, gm = [gens_g[jj] for jj in js], [gens_m[jj] for jj in js]
+            if meet == "y2t" and y2s is not None and y2s[0] == j:
+                y2s_fn = hip.spectral_y2s if self.y_mfma else hip.toeplitz_y2s
+                fn = lambda: y2s_fn(ny, C, rows, t2g, t2m, y2s[1], y2s[2], y2s[3], u2, plane=Cp)
+                self._launch("kernel:toeplitz_y2s", 8.0 * rows * C * 4 * ny, rows, self.y_stage_flop(2, 2, shared=True), fn)
+            elif meet == "y2t":
+                fn = lambda: hip.toeplitz_y2t(ny, C, rows, t2g, t2m, gg, gm, u2, plane=Cp)
+                self._launch("kernel:toeplitz_y2t", 8.0 * rows * C * 4 * ny, rows, self.y_stage_flop(2, 2), fn)
+            elif self.forms.y3t:
+                fn = lambda: hip.spectral_y3t(ny, C, rows, t2g, t2m, gg, gm, u2, plane=Cp)
+                self._launch("kernel:toeplitz_y", 8.0 * rows * C * ny * (2 + len(js)), rows, self.y_stage_flop(2, len(js)), fn)
+            else:
+                self._ystage(ny, C, rows, t2g, gg, u2, 0, ny, Cp)
+                self._ystage(ny, C, rows, t2m, gm, u2, 0, ny, Cp, accumulate=True)
+            for i, jj in enumerate(js):
+                self.backward_xz(u2[i], rows, 0, ny, [(0, ny, outs[jj], outs[jj].stride(0))])
 
     def flops_ss(self, rows_one, rows_two, nblocks, shared=False):
         """Executed flop of reduce_ss: rows_one one-term rows, rows_two two-term rows (forward transform per term, y stage, one second

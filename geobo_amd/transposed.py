@@ -54,7 +54,7 @@ class TransposedPosteriorMixin:
             rows_times_AT(blk(0, 0), self.Ms, 0, AkA[0:, 0:Msp])
             rows_times_AT(blk(0, 1), self.Ms, 1, AkA[0:, Msp:2 * Msp])
             rows_times_AT(blk(Msp, 1), Mm, 1, AkA[Msp:, Msp:2 * Msp])
-            AkA[Msp:2 * Msp, :Msp] = AkA[:Msp, Msp:2 * Msp].t()
+            hip.transpose(AkA[:Msp, Msp:2 * Msp], AkA[Msp:2 * Msp, :Msp])
             if Md:
                 rows_times_AT(blk(off_d, 0), Md, 0, AkA[off_d:, 0:Msp])
                 rows_times_AT(blk(off_d, 1), Md, 1, AkA[off_d:, Msp:2 * Msp])
@@ -176,8 +176,11 @@ class TransposedPosteriorMixin:
         else:
             ssum = torch.stack([t.sum(0).reshape(-1) for t in ss])                        # (P_c, N), voxel order (iy, ix, iz)
         if Md:
+            # K_2j[drill voxels, :]: the drill rows of A K, already there (fp64, every voxel column: _zpath_ok), zero rows behind them
+            Kd = [AK[2 * Msp:, jj * self.nc:(jj + 1) * self.nc] for jj in range(P_c)] if self.nc >= N and self.c0 == 0 else None
             ssum = ssum + self._timed("posterior_drill_rows", 0.0, lambda: self._drill_rows_ss(
-                step, Linv, 0, Md, (lambda Lv, n, func, out: self._lattice_Z(Lv, n, func, A_g if func == "grav" else A_m, out)) if lat else None, Ag, Am))
+                step, Linv, 0, Md, (lambda Lv, n, func, out: self._lattice_Z(Lv, n, func, A_g if func == "grav" else A_m, out)) if lat else None, Ag, Am,
+                Kd=Kd, y2s=None if zx else y2s))             # (zx: y2s holds the tables of the transposed planes)
         return mu_l, (amp * 1.0 - ssum).reshape(-1)
 
     def _mean_rows(self, step, w, vec_of):
@@ -204,19 +207,28 @@ class TransposedPosteriorMixin:
                 mu[jj].add_(tmp[jj][0])
         return mu
 
-    def _drill_rows_ss(self, step, Linv, d0, nd, lattice_Z, Ag, Am):
+    DRILL_SS_SLOTS = 4      # partial sums per column of the drill rows' squares (geobo_sumsq_accum: one thread per slot and column pair)
+
+    def _drill_rows_ss(self, step, Linv, d0, nd, lattice_Z, Ag, Am, Kd=None, y2s=None):
         """(P_c, N) sums of squares of V = L^-1 (A3 K) over the drill rows d0 .. d0 + nd of the row block behind the sensor rows:
-        L^-1 is lower triangular, so only THESE rows see the drill columns.  Tiles of up to 128 rows through the storing covariance
-        product, three terms (gravity, magnetic, drill block rows of K), squared and summed here.  lattice_Z(Lview, n, func, out):
-        rows of L^-1 A on a lattice survey; None: MFMA GEMMs against the resident operators Ag / Am (whole 128-row tiles)."""
+        L^-1 is lower triangular, so only THESE rows see the drill columns.  Tiles of up to 128 rows, three terms (gravity, magnetic,
+        drill block rows of K).  lattice_Z(Lview, n, func, out): rows of L^-1 A on a lattice survey; None: MFMA GEMMs against the
+        resident operators Ag / Am (whole 128-row tiles).
+        Kd[jj]: (>= Md rounded up to 16, >= N) view of K_2j[drill voxels, :] -- the drill rows of A K (engine._cov_rows), zero rows
+        behind them.  With it, on a lattice survey whose y stage joins two terms (sp.has_two_term_product) in batches that hold a
+        whole tile (sp.R >= 128): _drill_rows_ss_short.  Otherwise three storing products, added and squared here.
+        y2s: sp.y2s_tables of the step's untransposed tables where the caller has them (the short form builds them otherwise)."""
         props, sel_t, Md = step.props, step.sel_t, step.Md
         sp, N, Msp, P_c, T = self._spectral, self.N, self.Ms_pad, len(props), 128
-        Zgd, Zmd, Zdd = (self._workspace2d(nm, T, N) for nm in ("Zg_d", "Zm_d", "Zd_d"))
+        if Kd is not None and lattice_Z is not None and sp.has_two_term_product(P_c) and sp.R >= T:
+            return self._drill_rows_ss_short(step, Linv, d0, nd, lattice_Z, Kd, y2s)
+        Zgd, Zmd = (self._workspace2d(nm, T, N) for nm in ("Zg_d", "Zm_d"))
         Vd = [self._workspace2d("Vd_%d" % jj, T, N) for jj in range(P_c)]
         tmp = [self._workspace2d("Vt_%d" % jj, T, N) for jj in range(P_c)]
         gens_g, gens_m = [step.gens[(0, j)] for j in props], [step.gens[(1, j)] for j in props]
-        gens_d = [sp.eigenvalues(step.prior.table(self, 2, j)) for j in props]
         acc = torch.zeros((P_c, N), dtype=F64, device=self.device)
+        Zdd = self._workspace2d("Zd_d", T, N)
+        gens_d = [sp.eigenvalues(step.prior.table(self, 2, j)) for j in props]
         for c0 in range(d0, d0 + nd, T):
             n = min(T, d0 + nd - c0)
             b0 = 2 * Msp + c0
@@ -237,3 +249,32 @@ class TransposedPosteriorMixin:
             for jj in range(P_c):
                 acc[jj].add_((Vd[jj][:n] ** 2).sum(0))
         return acc
+
+    def _drill_rows_ss_short(self, step, Linv, d0, nd, lattice_Z, Kd, y2s=None):
+        """_drill_rows_ss without the third spectral product and without torch arithmetic: the two sensor terms meet in the y stage
+        (sp.product_two_term: ONE stored V per block), the drill term is the small product L^-1[rows, drill columns] Kd[jj] (Md deep:
+        K_2j[drill voxels, :] is already there), and geobo_sumsq_accum adds the two, squares and sums over the rows."""
+        props, Md = step.props, step.Md
+        sp, N, Msp, P_c, T = self._spectral, self.N, self.Ms_pad, len(props), 128
+        Zgd, Zmd = (self._workspace2d(nm, T, N) for nm in ("Zg_d", "Zm_d"))
+        Vd = [self._workspace2d("Vd_%d" % jj, T, N) for jj in range(P_c)]
+        tmp = [self._workspace2d("Vt_%d" % jj, T, N) for jj in range(P_c)]
+        gens_g, gens_m = [step.gens[(0, j)] for j in props], [step.gens[(1, j)] for j in props]
+        if y2s is None and tuple(props[:2]) == (0, 1):
+            y2s = sp.y2s_tables(gens_g, gens_m, check=False)   # (the caller's pass over these blocks has left their sym_residual)
+        kd = (Md + 15) // 16 * 16
+        Ld = self._workspace2d("Ld_d", T, kd)                  # the rows' drill columns of L^-1, zero padded to the GEMM's extents
+        ss = self._workspace("drill_ss", (P_c, self.DRILL_SS_SLOTS, N))
+        ss.zero_()
+        for c0 in range(d0, d0 + nd, T):
+            n = min(T, d0 + nd - c0)
+            b0 = 2 * Msp + c0
+            lattice_Z(Linv[b0:b0 + n, :Msp], n, "grav", Zgd)
+            lattice_Z(Linv[b0:b0 + n, Msp:2 * Msp], n, "magn", Zmd)
+            sp.product_two_term(Zgd, Zmd, n, gens_g, gens_m, Vd, y2s=y2s)
+            Ld.zero_()
+            Ld[:n, :Md] = Linv[b0:b0 + n, 2 * Msp:2 * Msp + Md]
+            for jj in range(P_c):
+                hip.gemm_batched(True, T, N, kd, Ld, Ld.stride(0), 0, Kd[jj], Kd[jj].stride(0), 0, tmp[jj], tmp[jj].stride(0), 0, n, N, 1)
+                hip.sumsq_accum(Vd[jj], tmp[jj], n, ss[jj])
+        return ss.sum(1)

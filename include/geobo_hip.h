@@ -241,9 +241,11 @@ int geobo_gemm_nn(int64_t m, int64_t n, int64_t k, double alpha, const double* X
 /* Batched form of the two products above with store predicates: for b < batch
  *     C_b[:m_valid, :n_valid] = alpha * X_b * op(Y_b) + beta * C_b,   X_b = X + b*strideX etc. (stride 0 = shared operand)
  * y_is_kn = 0: Y_b is n x k (k-contiguous, "NT");  y_is_kn = 1: Y_b is k x n (n-contiguous, "NN").
+ * y_is_kn | GEOBO_GEMM_X_KM (NT only): X_b is given transposed, k x m (m-contiguous, ldx = distance of its k-rows).
  * m, n are the COMPUTE extents (multiples of 128; operands must be readable over them), m_valid <= m and n_valid <= n
  * the stored extents.  Used by the spectral (real-DFT) form of the covariance product: every axis pass of the 3-D
  * transform is a batch of small-k MFMA GEMMs against a fixed cosine/sine matrix. */
+#define GEOBO_GEMM_X_KM 2
 int geobo_gemm_batched(int y_is_kn, int64_t m, int64_t n, int64_t k, double alpha, const double* X, int64_t ldx,
                        int64_t strideX, const double* Y, int64_t ldy, int64_t strideY, double beta, double* C, int64_t ldc,
                        int64_t strideC, int64_t m_valid, int64_t n_valid, int batch, void* stream);
@@ -548,6 +550,9 @@ int geobo_lamdot_z(int64_t batch, int planes, int px, int nz, const double* D, c
  * that is not 16-byte aligned and ld < n); ld even (GEOBO_E_ALIGN); n may be odd (the middle row is then a source only).  The
  * columns n .. ld-1 are not touched.  16-byte loads of the source row, reversed in registers; one read + one write of half the block. */
 int geobo_centro_fill(double* B, int64_t ld, int64_t n, int64_t r0, void* stream);
+/* dst[c][r] = src[r][c] for r < rows, c < cols (lds >= cols, ldd >= rows, rows <= 64 * 65535: GEOBO_E_ARG otherwise); src and dst
+ * must not overlap.  The block of AkA below the diagonal that is the transpose of a computed one.  64 x 64 tiles through LDS. */
+int geobo_transpose(int64_t rows, int64_t cols, const double* src, int64_t lds, double* dst, int64_t ldd, void* stream);
 /* The same mirror on rows of A_m K_11 (inversion.py:96's left factor), for readers of the rows a mirrored step did not compute:
  *     X[r][b][z] = X[m-1-r][nb-1-b][z]   for r0 <= r < m, b < nb voxel columns (iy, ix), z < nz
  * 2 r0 >= m, nb nz <= ld (GEOBO_E_ARG); nz, ld even, X 16-byte aligned (GEOBO_E_ALIGN). */
