@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "cutoff_set.h"
 #include "geobo_hip.h"
 
 namespace {
@@ -37,7 +38,6 @@ namespace {
 constexpr int WG = 256;
 constexpr int TILE = 512;             // voxels of a tile of the tile-local phase at most
 constexpr int CHUNK = 2 * WG;       // voxels of a sum chunk (as in gradetonnage.hip)
-constexpr int CMAX = 32;
 constexpr int64_t VMAX = 65535;     // volumes of a call (grid y extent)
 constexpr int NSTAT = 6;            // count_total, n_bodies, largest count, largest label, seeded count, seeded bodies
 constexpr int NSUM = 3;             // whole set, largest body, seeded body
@@ -456,41 +456,26 @@ extern "C" int geobo_bodies(int64_t S, const double* F, int64_t sstride, int64_t
                             int32_t* info, int phases, void* ws, size_t ws_bytes, void* stream) {
   // every check before any device access (t, lo and seeds are host arrays)
   Grid g;
-  if (!F || !t || !lo || !stats || !sums || !info || !ws) return GEOBO_E_ARG;
-  if (!grid_of(ny, nx, nz, g) || !shape_ok(S, C) || p < 0 || p > 2) return GEOBO_E_ARG;
+  if (!stats || !sums || !info || !ws) return GEOBO_E_ARG;
+  if (!grid_of(ny, nx, nz, g) || !shape_ok(S, C)) return GEOBO_E_ARG;
   if (neighbours != 6 && neighbours != 26) return GEOBO_E_ARG;
   if (min_count < 1 || K < 0 || K > g.n || (K > 0 && !seeds)) return GEOBO_E_ARG;
   if (phases < 1 || phases > (GEOBO_BODIES_ALL | GEOBO_BODIES_TILED) || !(phases & GEOBO_BODIES_ALL)) return GEOBO_E_ARG;
-  for (int c = 0; c < C; ++c) {
-    if (t[c] != t[c] || (c > 0 && t[c] < t[c - 1])) return GEOBO_E_ARG;     // NaN, or not ascending
-  }
-  for (int q = 0; q < 3; ++q) {
-    if (lo[q] != lo[q]) return GEOBO_E_ARG;
-  }
   for (int64_t k = 0; k < K; ++k) {
     if (seeds[k] < 0 || seeds[k] >= g.n) return GEOBO_E_ARG;
   }
   const int64_t n = g.n;
-  if (pstride < n || pstride > INT64_MAX / 4 || sstride < 2 * pstride + n) return GEOBO_E_ARG;
-  if (S > 0 && sstride > INT64_MAX / S) return GEOBO_E_ARG;
+  BodyArgs a{};
+  if (!cutoff_set_of(S, F, sstride, pstride, n, p, C, t, lo, mask, a)) return GEOBO_E_ARG;
   const Layout l = layout_of(S, n, C);
   if (ws_bytes < l.total || ((uintptr_t)ws & 15)) return GEOBO_E_ARG;
   if (S == 0) return GEOBO_OK;
 
   const int64_t V = S * C;
   char* w8 = (char*)ws;
-  BodyArgs a{};
-  a.F = F; a.sstride = sstride; a.pstride = pstride; a.n = n;
-  a.S = (int)S; a.C = C; a.ny = ny; a.nx = nx; a.nz = nz;
+  a.pstride = pstride; a.S = (int)S; a.ny = ny; a.nx = nx; a.nz = nz;
   a.cap = (int)(2 * n + 64 > INT32_MAX ? INT32_MAX : 2 * n + 64);
-  for (int j = 0; j < 3; ++j) {
-    const int q = (p + j) % 3;
-    a.off[j] = q * pstride;
-    a.lo[j] = lo[q];
-    a.read[j] = j == 0 || lo[q] > -INFINITY;
-  }
-  for (int c = 0; c < CMAX; ++c) a.t[c] = c < C ? t[c] : 0.0;
-  a.mask = mask; a.weight = weight; a.info = info;
+  a.weight = weight; a.info = info;
   a.L = (int32_t*)(w8 + l.L);
   a.label = labels ? labels : (int32_t*)(w8 + l.label);
   a.size = (int64_t*)(w8 + l.size);

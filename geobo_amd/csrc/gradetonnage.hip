@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "cutoff_set.h"
 #include "geobo_hip.h"
 
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -31,7 +32,6 @@ namespace {
 
 constexpr int WG = 256;             // lanes of a cutoff workgroup
 constexpr int CHUNK = 2 * WG;       // elements of a chunk
-constexpr int CMAX = 32;            // thresholds at most
 constexpr int64_t S_LAUNCH = 32768; // samples per launch (16-bit histogram counters)
 
 // ---- box means -----------------------------------------------------------------------------------------------------------------
@@ -288,31 +288,14 @@ extern "C" int geobo_cutoff_stats(int64_t S, const double* F, int64_t sstride, i
                                   const double* lo, const uint8_t* mask, const int32_t* weight, int64_t* cnt, double* sum,
                                   uint32_t* hits, void* ws, size_t ws_bytes, void* stream) {
   // every check before any device access (t and lo are host arrays)
-  if (!F || !t || !lo || !cnt || !sum || !ws) return GEOBO_E_ARG;
-  if (!cut_shape_ok(S, n, C) || p < 0 || p > 2) return GEOBO_E_ARG;
-  for (int c = 0; c < C; ++c) {
-    if (t[c] != t[c] || (c > 0 && t[c] < t[c - 1])) return GEOBO_E_ARG;     // NaN, or not ascending
-  }
-  for (int q = 0; q < 3; ++q) {
-    if (lo[q] != lo[q]) return GEOBO_E_ARG;
-  }
-  if (pstride < n || pstride > INT64_MAX / 4 || sstride < 2 * pstride + n) return GEOBO_E_ARG;
-  if (S > 0 && sstride > INT64_MAX / S) return GEOBO_E_ARG;
+  CutArgs a{};
+  if (!cnt || !sum || !ws || !cut_shape_ok(S, n, C)) return GEOBO_E_ARG;
+  if (!cutoff_set_of(S, F, sstride, pstride, n, p, C, t, lo, mask, a)) return GEOBO_E_ARG;
   const size_t need = cut_ws_bytes_of(S, n, C);
   if (need == 0 || ws_bytes < need || ((uintptr_t)ws & 15)) return GEOBO_E_ARG;
   if (S == 0) return GEOBO_OK;
 
-  CutArgs a{};
-  a.sstride = sstride; a.pstride = pstride; a.n = n;
-  a.C = C;
-  for (int j = 0; j < 3; ++j) {
-    const int q = (p + j) % 3;
-    a.off[j] = q * pstride;
-    a.lo[j] = lo[q];
-    a.read[j] = j == 0 || lo[q] > -INFINITY;
-  }
-  for (int c = 0; c < CMAX; ++c) a.t[c] = c < C ? t[c] : 0.0;
-  a.mask = mask; a.weight = weight; a.hits = hits;
+  a.pstride = pstride; a.weight = weight; a.hits = hits;
   a.nchunks = (n + CHUNK - 1) / CHUNK;
   hipStream_t st = (hipStream_t)stream;
   for (int64_t s0 = 0; s0 < S; s0 += S_LAUNCH) {              // stream order lets the launches share ws

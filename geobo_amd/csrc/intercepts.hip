@@ -21,11 +21,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "cutoff_set.h"
 #include "geobo_hip.h"
 
 namespace {
 
-constexpr int CMAX = 32;            // thresholds at most
 constexpr int LCAP = 4096;          // positions of a trace at most (13 bits of the packed partial hold 0 .. 4096)
 constexpr int WAVES = 4;            // traces of a workgroup
 
@@ -280,18 +280,10 @@ extern "C" int geobo_trace_stats(int64_t S, const double* F, int64_t sstride, in
                                  uint32_t* hits, int64_t* thick_sum, int64_t* top_sum, double* acc_sum, uint32_t* hist_len,
                                  uint32_t* hist_thick, int32_t* detail, double* dsum, void* ws, size_t ws_bytes, void* stream) {
   // every check before any device access (t and lo are host arrays; offsets and voxels are on the device and are not read here)
-  if (!F || !t || !lo || !tab || !ws) return GEOBO_E_ARG;
-  if (!trace_shape_ok(S, K, C) || p < 0 || p > 2) return GEOBO_E_ARG;
+  if (!tab || !ws || !trace_shape_ok(S, K, C)) return GEOBO_E_ARG;
   if (ny < 1 || nx < 1 || nz < 1 || (int64_t)ny * nx > INT32_MAX / nz) return GEOBO_E_ARG;
-  const int64_t n = (int64_t)ny * nx * nz;
-  for (int c = 0; c < C; ++c) {
-    if (t[c] != t[c] || (c > 0 && t[c] < t[c - 1])) return GEOBO_E_ARG;     // NaN, or not ascending
-  }
-  for (int q = 0; q < 3; ++q) {
-    if (lo[q] != lo[q]) return GEOBO_E_ARG;
-  }
-  if (pstride < n || pstride > INT64_MAX / 4 || sstride < 2 * pstride + n) return GEOBO_E_ARG;
-  if (S > 0 && sstride > INT64_MAX / S) return GEOBO_E_ARG;
+  TraceArgs a{};
+  if (!cutoff_set_of(S, F, sstride, pstride, (int64_t)ny * nx * nz, p, C, t, lo, mask, a)) return GEOBO_E_ARG;
   if (min_len < 1 || max_gap < 0 || max_gap > LCAP || Lmax < 1 || Lmax > LCAP) return GEOBO_E_ARG;
   if (voxels) {
     if (!offsets) return GEOBO_E_ARG;
@@ -302,17 +294,9 @@ extern "C" int geobo_trace_stats(int64_t S, const double* F, int64_t sstride, in
   if (need == 0 || ws_bytes < need || ((uintptr_t)ws & 15)) return GEOBO_E_ARG;
   if (S == 0) return GEOBO_OK;
 
-  TraceArgs a{};
-  a.F = F; a.sstride = sstride; a.n = n; a.S = S; a.K = K;
-  a.C = C; a.nz = nz; a.Lmax = Lmax; a.min_len = min_len; a.max_gap = max_gap;
-  for (int j = 0; j < 3; ++j) {
-    const int q = (p + j) % 3;
-    a.off[j] = q * pstride;
-    a.lo[j] = lo[q];
-    a.read[j] = j == 0 || lo[q] > -INFINITY;
-  }
-  for (int c = 0; c < CMAX; ++c) a.t[c] = c < C ? t[c] : 0.0;
-  a.mask = mask; a.offsets = offsets; a.voxels = voxels;
+  a.S = S; a.K = K;
+  a.nz = nz; a.Lmax = Lmax; a.min_len = min_len; a.max_gap = max_gap;
+  a.offsets = offsets; a.voxels = voxels;
   a.hits_any = hits_any; a.hits = hits; a.thick_sum = thick_sum; a.top_sum = top_sum; a.acc_sum = acc_sum;
   a.hist_len = hist_len; a.hist_thick = hist_thick; a.detail = detail; a.dsum = dsum;
   a.part = (int32_t*)ws;

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .resources import QUANTILES
+from .resources import _block_support, _check_batch, nanmean, nanquantile, tonnage
 
 NEIGHBOURS = (6, 26)
 PROBABILITY = (None, "largest", "seeded", "both")
@@ -82,16 +82,6 @@ def renumber(labels):
     return out.reshape(lab.shape), sizes.astype(np.int64)
 
 
-def _q3(a):
-    a = np.asarray(a, dtype=np.float64)
-    res = np.full((3, a.shape[1]), np.nan)
-    for j in range(a.shape[1]):
-        col = a[:, j]
-        if not np.isnan(col).all():
-            res[:, j] = np.nanquantile(col, QUANTILES)
-    return res
-
-
 def body_tables(stats, sums, scale, offset, voxel_volume):
     """(n, C, 6) int64 statistics and (n, C, 3) sums (normalised units) of geobo_bodies -> dict: `count` (the whole set), `n_bodies`,
     `largest` and `seeded` = dicts of count, volume = count x voxel volume, quantity = (scale x sum + offset x count) x voxel volume
@@ -99,21 +89,13 @@ def body_tables(stats, sums, scale, offset, voxel_volume):
     quantiles over the realisations of n_bodies, the largest volume and the seeded volume, (3, C) each."""
     stats = np.asarray(stats, dtype=np.int64)
     sums = np.asarray(sums, dtype=np.float64)
-    vv = float(voxel_volume)
-
-    def part(count, total):
-        volume = count * vv
-        quantity = (float(scale) * total + float(offset) * count) * vv
-        with np.errstate(all="ignore"):
-            grade = np.where(count > 0, quantity / np.where(count > 0, volume, 1.0), np.nan)
-        return dict(count=count, volume=volume, quantity=quantity, grade=grade)
     out = dict(count=stats[..., 0].copy(), n_bodies=stats[..., 1].copy())
-    out["largest"] = part(stats[..., 2].copy(), sums[..., 1])
+    out["largest"] = tonnage(stats[..., 2].copy(), sums[..., 1], scale, offset, voxel_volume)
     out["largest"]["label"] = stats[..., 3].copy()
-    out["seeded"] = part(stats[..., 4].copy(), sums[..., 2])
+    out["seeded"] = tonnage(stats[..., 4].copy(), sums[..., 2], scale, offset, voxel_volume)
     out["seeded"]["bodies"] = stats[..., 5].copy()
-    out["quantiles"] = dict(n_bodies=_q3(out["n_bodies"]), largest_volume=_q3(out["largest"]["volume"]),
-                            seeded_volume=_q3(out["seeded"]["volume"]))
+    out["quantiles"] = dict(n_bodies=nanquantile(out["n_bodies"]), largest_volume=nanquantile(out["largest"]["volume"]),
+                            seeded_volume=nanquantile(out["seeded"]["volume"]))
     return out
 
 
@@ -125,14 +107,6 @@ def bodies_frame(out):
     """One row per cutoff: CUTOFF, P10 / P50 / P90 / MEAN of the number of bodies, the largest and the seeded volume, and the mean
     grades of both bodies and the mean number of seeded bodies (a pandas DataFrame)."""
     import pandas as pd
-
-    def nanmean(a):
-        a = np.asarray(a, dtype=np.float64)
-        res = np.full(a.shape[1], np.nan)
-        for j in range(a.shape[1]):
-            if not np.isnan(a[:, j]).all():
-                res[j] = np.nanmean(a[:, j])
-        return res
     cols = {"CUTOFF": np.asarray(out["cutoffs"], dtype=np.float64)}
     for name, key, table in (("BODIES", "n_bodies", out["n_bodies"]), ("LARGEST_VOLUME", "largest_volume", out["largest"]["volume"]),
                              ("SEEDED_VOLUME", "seeded_volume", out["seeded"]["volume"])):
@@ -172,27 +146,13 @@ class GeobodyMixin:
         box = (by, bx, bz): geobo_box_means first, then the block grid is labelled with the blocks' voxel counts as weights.
         A batch is cut into launches of at most ws_bytes of workspace; the cut changes no bit.  BodyStatisticsError when a bounded
         walk of the union-find ran out (the call reads one word back from the device)."""
-        if self.world > 1:
-            raise NotImplementedError("body statistics run on one rank (world = %d)" % self.world)
-        if not (isinstance(F, torch.Tensor) and F.dim() == 3 and F.shape[1] == 3 and F.shape[2] == self.N):
-            raise ValueError("F must be a (S, 3, %d) device tensor" % self.N)
+        _check_batch(self, F, "body statistics")
         neighbours = check_neighbours(neighbours)
         with torch.cuda.device(self.device):
-            S = F.shape[0]
             t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
             C_ = int(t.size)
-            grid = (self.ny, self.nx, self.nz)
-            weight = None
-            if box is not None:
-                from .blocksupport import block_counts, check_box
-                box = check_box(box, grid)
-                nb = block_counts(grid, box)
-                nblocks = nb[0] * nb[1] * nb[2]
-                G = self._workspace("tonnage_means", (max(S, 1) * 3 * nblocks,))[:S * 3 * nblocks].view(S, 3, nblocks)
-                weight = self._workspace("tonnage_count", (nblocks,), dtype=torch.int32)
-                self._timed("box_means", 0.0, lambda: hip.box_means(F, grid, box, G=G, count=weight))
-                F, grid = G, nb
-            n = F.shape[2]
+            F, grid, weight = _block_support(self, F, box)
+            S, n = F.shape[0], F.shape[2]
             stats = torch.empty((S, C_, len(hip.BODY_STATS)), dtype=torch.int64, device=F.device)
             sums = torch.empty((S, C_, len(hip.BODY_SUMS)), dtype=torch.float64, device=F.device)
             info = torch.zeros(1, dtype=torch.int32, device=F.device)

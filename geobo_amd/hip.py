@@ -1022,6 +1022,47 @@ def _samples(F, name):
     return F.shape[0], F.shape[2], F.stride(0), F.stride(1)
 
 
+def _cutoff_batch(F, grid, thresholds, lo, mask, weight):
+    """A batch of realisations F (S, 3, n) against a cutoff set: the checks and host arrays that cutoff_stats, bodies and trace_stats
+    share.  grid: (ny, nx, nz) holding the n elements, or None.  Returns (S, n, sample stride, property stride, t, lo_h, C)."""
+    S, n, ss, ps = _samples(F, "F")
+    if grid is not None and (len(grid) != 3 or n != grid[0] * grid[1] * grid[2]):
+        raise ValueError("F holds %d elements per property, the grid %r does not" % (n, grid))
+    t = np.array(thresholds, dtype=np.float64).reshape(-1)         # (own copies: contiguous and writable, as _doubles needs them)
+    lo_h = np.full(3, -np.inf) if lo is None else np.array(lo, dtype=np.float64).reshape(-1)
+    if lo_h.size != 3:
+        raise ValueError("lo holds one lower bound per property")
+    for x, name, dtype in ((mask, "mask", torch.uint8), (weight, "weight", torch.int32)):
+        if x is not None:
+            _chk(x, name, dtype)
+            assert x.is_contiguous() and x.numel() == n
+    return S, n, ss, ps, t, lo_h, t.size
+
+
+def _int32(h, name, shape):
+    """An optional contiguous int32 tensor of the given shape (the kernels' uint32 counters travel so: torch has no arithmetic on uint32)."""
+    if h is not None:
+        _chk(h, name, torch.int32)
+        assert h.is_contiguous() and tuple(h.shape) == tuple(shape), name
+
+
+def _opt(x):
+    """The device pointer of an optional tensor (NULL for None)."""
+    return C.c_void_p(None) if x is None else _p(x)
+
+
+def _doubles(a):
+    """A contiguous writable fp64 host array as the C array the ABI takes for `const double*` (it keeps `a` alive)."""
+    return (C.c_double * a.size).from_buffer(a)
+
+
+def _ws_or_new(ws, need, device):
+    """ws if it holds `need` doubles, a new workspace otherwise."""
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=F64, device=device)
+    return _chk(ws, "ws")
+
+
 def box_means(F, grid, box, G=None, count=None):
     """Means of the S realisations F (S, 3, N; voxel order (iy, ix, iz)) over the boxes of `box` = (by, bx, bz) voxels tiling `grid` =
     (ny, nx, nz) from the origin (partial at the far edges; block index (jy nbx + jx) nbz + jz): returns (G (S, 3, nblocks) fp64,
@@ -1059,32 +1100,13 @@ def cutoff_stats(F, p, thresholds, lo=None, mask=None, weight=None, hits=None, w
     sum of the weights (weight: (n,) int32, None = 1) of the passing elements, sum (S, C) fp64 = sum of weight x value); hits
     ((C, n) int32 or None) is incremented by one per passing sample.  Bitwise reproducible, the same for any grouping of samples."""
     lib = require_gpu()
-    S, n, ss, ps = _samples(F, "F")
-    t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    lo_h = np.ascontiguousarray(np.full(3, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1))
-    C_ = t.size
-    if lo_h.size != 3:
-        raise ValueError("lo holds one lower bound per property")
-    dev = F.device
-    if mask is not None:
-        _chk(mask, "mask", torch.uint8)
-        assert mask.is_contiguous() and mask.numel() == n
-    if weight is not None:
-        _chk(weight, "weight", torch.int32)
-        assert weight.is_contiguous() and weight.numel() == n
-    if hits is not None:
-        _chk(hits, "hits", torch.int32)             # (the kernel's uint32 counters: torch has no arithmetic on uint32)
-        assert hits.is_contiguous() and tuple(hits.shape) == (C_, n)
-    need = cutoff_stats_ws_doubles(S, n, C_)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=F64, device=dev)
-    cnt = torch.empty((S, C_), dtype=torch.int64, device=dev)
-    tot = torch.empty((S, C_), dtype=F64, device=dev)
-    null = C.c_void_p(None)
-    _lib.check(lib.geobo_cutoff_stats(S, _p(F), ss, ps, n, int(p), C_, t.ctypes.data_as(C.POINTER(C.c_double)),
-                                      lo_h.ctypes.data_as(C.POINTER(C.c_double)), null if mask is None else _p(mask),
-                                      null if weight is None else _p(weight), _p(cnt), _p(tot), null if hits is None else _p(hits),
-                                      _p(_chk(ws, "ws")), ws.numel() * 8, _stream()), "geobo_cutoff_stats")
+    S, n, ss, ps, t, lo_h, C_ = _cutoff_batch(F, None, thresholds, lo, mask, weight)
+    _int32(hits, "hits", (C_, n))
+    ws = _ws_or_new(ws, cutoff_stats_ws_doubles(S, n, C_), F.device)
+    cnt = torch.empty((S, C_), dtype=torch.int64, device=F.device)
+    tot = torch.empty((S, C_), dtype=F64, device=F.device)
+    _lib.check(lib.geobo_cutoff_stats(S, _p(F), ss, ps, n, int(p), C_, _doubles(t), _doubles(lo_h), _opt(mask), _opt(weight), _p(cnt), _p(tot),
+                                      _opt(hits), _p(ws), ws.numel() * 8, _stream()), "geobo_cutoff_stats")
     return cnt, tot
 
 
@@ -1110,33 +1132,14 @@ def bodies(F, grid, p, thresholds, lo=None, mask=None, weight=None, neighbours=6
     smallest voxel index of each voxel's body, -1 outside.  Exact counts, bitwise reproducible sums.  tiled=False: the merge stage
     without its tile-local phase in LDS (the same results, slower)."""
     lib = require_gpu()
-    S, n, ss, ps = _samples(F, "F")
     grid = tuple(int(v) for v in grid)
-    if len(grid) != 3 or n != grid[0] * grid[1] * grid[2]:
-        raise ValueError("F holds %d elements per property, the grid %r does not" % (n, grid))
-    t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    lo_h = np.ascontiguousarray(np.full(3, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1))
-    C_ = t.size
-    if lo_h.size != 3:
-        raise ValueError("lo holds one lower bound per property")
+    S, n, ss, ps, t, lo_h, C_ = _cutoff_batch(F, grid, thresholds, lo, mask, weight)
     dev = F.device
-    if mask is not None:
-        _chk(mask, "mask", torch.uint8)
-        assert mask.is_contiguous() and mask.numel() == n
-    if weight is not None:
-        _chk(weight, "weight", torch.int32)
-        assert weight.is_contiguous() and weight.numel() == n
-    for h, name in ((hits_largest, "hits_largest"), (hits_seeded, "hits_seeded")):
-        if h is not None:
-            _chk(h, name, torch.int32)                # (the kernel's uint32 counters: torch has no arithmetic on uint32)
-            assert h.is_contiguous() and tuple(h.shape) == (C_, n)
-    if labels is not None:
-        _chk(labels, "labels", torch.int32)
-        assert labels.is_contiguous() and tuple(labels.shape) == (S, C_, n)
+    _int32(hits_largest, "hits_largest", (C_, n))
+    _int32(hits_seeded, "hits_seeded", (C_, n))
+    _int32(labels, "labels", (S, C_, n))
     sd = np.ascontiguousarray(np.zeros(0, dtype=np.int32) if seeds is None else np.asarray(seeds, dtype=np.int32).reshape(-1))
-    need = bodies_ws_doubles(S, grid, C_)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=F64, device=dev)
+    ws = _ws_or_new(ws, bodies_ws_doubles(S, grid, C_), dev)
     if info is None:
         info = torch.zeros(1, dtype=torch.int32, device=dev)
     _chk(info, "info", torch.int32)
@@ -1147,12 +1150,10 @@ def bodies(F, grid, p, thresholds, lo=None, mask=None, weight=None, neighbours=6
     _chk(stats, "stats", torch.int64)
     _chk(sums, "sums")
     assert stats.is_contiguous() and tuple(stats.shape) == (S, C_, 6) and sums.is_contiguous() and tuple(sums.shape) == (S, C_, 3)
-    null = C.c_void_p(None)
-    opt = lambda x: null if x is None else _p(x)
-    _lib.check(lib.geobo_bodies(S, _p(F), ss, ps, *grid, int(p), C_, t.ctypes.data_as(C.POINTER(C.c_double)),
-                                lo_h.ctypes.data_as(C.POINTER(C.c_double)), opt(mask), opt(weight), int(neighbours), int(min_count), sd.size,
-                                sd.ctypes.data_as(C.POINTER(C.c_int32)), _p(stats), _p(sums), opt(hits_largest), opt(hits_seeded), opt(labels),
-                                _p(info), int(phases) | (BODIES_TILED if tiled else 0), _p(_chk(ws, "ws")), ws.numel() * 8, _stream()), "geobo_bodies")
+    _lib.check(lib.geobo_bodies(S, _p(F), ss, ps, *grid, int(p), C_, _doubles(t), _doubles(lo_h), _opt(mask), _opt(weight), int(neighbours),
+                                int(min_count), sd.size, sd.ctypes.data_as(C.POINTER(C.c_int32)), _p(stats), _p(sums), _opt(hits_largest),
+                                _opt(hits_seeded), _opt(labels), _p(info), int(phases) | (BODIES_TILED if tiled else 0), _p(ws), ws.numel() * 8,
+                                _stream()), "geobo_bodies")
     if sd.size and (phases & BODIES_STATS):
         torch.cuda.current_stream().synchronize()     # the staging copy of the host seeds has been read before `sd` goes away
     return stats, sums, info
@@ -1228,23 +1229,11 @@ def trace_stats(F, grid, p, thresholds, lo=None, mask=None, traces=None, min_len
     (trace_maps; any subset), incremented; detail (S, C, K, 6) int32 -- TRACE_DETAIL -- and dsum (S, C, K, 2) fp64 -- TRACE_DSUM --
     are written when given.  Exact integers, bitwise reproducible sums, the same for any grouping of samples."""
     lib = require_gpu()
-    S, n, ss, ps = _samples(F, "F")
     grid = tuple(int(v) for v in grid)
-    if len(grid) != 3 or n != grid[0] * grid[1] * grid[2]:
-        raise ValueError("F holds %d elements per property, the grid %r does not" % (n, grid))
-    t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
-    lo_h = np.ascontiguousarray(np.full(3, -np.inf) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1))
-    C_ = t.size
-    if lo_h.size != 3:
-        raise ValueError("lo holds one lower bound per property")
+    S, n, ss, ps, t, lo_h, C_ = _cutoff_batch(F, grid, thresholds, lo, mask, None)
     dev = F.device
-    if mask is not None:
-        _chk(mask, "mask", torch.uint8)
-        assert mask.is_contiguous() and mask.numel() == n
-    null = C.c_void_p(None)
-    opt = lambda x: null if x is None else _p(x)
     if traces is None:
-        K, Lmax, off_p, vox_p = grid[0] * grid[1], grid[2], null, null
+        K, Lmax, off_p, vox_p = grid[0] * grid[1], grid[2], _opt(None), _opt(None)
     else:
         if not isinstance(traces, TraceSet) or traces.n != n:
             raise ValueError("traces is a TraceSet validated for the %d voxels of F" % n)
@@ -1256,12 +1245,10 @@ def trace_stats(F, grid, p, thresholds, lo=None, mask=None, traces=None, min_len
         if m is not None:
             _chk(m, name, dtype)                      # (the kernel's uint32 counters travel as int32: torch has no arithmetic on uint32)
             assert m.is_contiguous() and tuple(m.shape) == ((C_, K, Lmax + 1) if name.startswith("hist") else (C_, K)), name
-        ptr[name] = opt(m)
+        ptr[name] = _opt(m)
     if set(maps) - set(ptr):
         raise ValueError("unknown maps %r" % sorted(set(maps) - set(ptr)))
-    if detail is not None:
-        _chk(detail, "detail", torch.int32)
-        assert detail.is_contiguous() and tuple(detail.shape) == (S, C_, K, 6)
+    _int32(detail, "detail", (S, C_, K, 6))
     if dsum is not None:
         _chk(dsum, "dsum")
         assert dsum.is_contiguous() and tuple(dsum.shape) == (S, C_, K, 2)
@@ -1269,13 +1256,10 @@ def trace_stats(F, grid, p, thresholds, lo=None, mask=None, traces=None, min_len
         tab = torch.empty((S, C_, 3), dtype=torch.int64, device=dev)
     _chk(tab, "tab", torch.int64)
     assert tab.is_contiguous() and tuple(tab.shape) == (S, C_, 3)
-    need = trace_stats_ws_doubles(S, K, C_)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=F64, device=dev)
-    _lib.check(lib.geobo_trace_stats(S, _p(F), ss, ps, *grid, int(p), C_, t.ctypes.data_as(C.POINTER(C.c_double)),
-                                     lo_h.ctypes.data_as(C.POINTER(C.c_double)), opt(mask), K, off_p, vox_p, Lmax, int(min_len), int(max_gap),
-                                     _p(tab), ptr["hits_any"], ptr["hits"], ptr["thick_sum"], ptr["top_sum"], ptr["acc_sum"],
-                                     ptr["hist_len"], ptr["hist_thick"], opt(detail), opt(dsum), _p(_chk(ws, "ws")), ws.numel() * 8,
+    ws = _ws_or_new(ws, trace_stats_ws_doubles(S, K, C_), dev)
+    _lib.check(lib.geobo_trace_stats(S, _p(F), ss, ps, *grid, int(p), C_, _doubles(t), _doubles(lo_h), _opt(mask), K, off_p, vox_p, Lmax,
+                                     int(min_len), int(max_gap), _p(tab), ptr["hits_any"], ptr["hits"], ptr["thick_sum"], ptr["top_sum"],
+                                     ptr["acc_sum"], ptr["hist_len"], ptr["hist_thick"], _opt(detail), _opt(dsum), _p(ws), ws.numel() * 8,
                                      _stream()), "geobo_trace_stats")
     return tab
 

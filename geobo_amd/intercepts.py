@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .resources import QUANTILES
+from .resources import QUANTILES, _check_batch
 
 WS_BYTES = 1 << 30                  # bound of the workspace plus the per-hole tables of one geobo_trace_stats launch
 LMAX = hip.TRACE_LMAX
@@ -305,10 +305,7 @@ class InterceptMixin:
         accumulators (hip.trace_maps) incremented by the batch, or None.  Returns tab (S, C, 3) int64 (hip.TRACE_TAB) and with detail
         (tab, detail (S, C, K, 6) int32, dsum (S, C, K, 2) fp64) -- hip.TRACE_DETAIL, hip.TRACE_DSUM.  A batch is cut into launches
         whose workspace and per-hole tables stay below ws_bytes; the cut changes no bit."""
-        if self.world > 1:
-            raise NotImplementedError("trace statistics run on one rank (world = %d)" % self.world)
-        if not (isinstance(F, torch.Tensor) and F.dim() == 3 and F.shape[1] == 3 and F.shape[2] == self.N):
-            raise ValueError("F must be a (S, 3, %d) device tensor" % self.N)
+        _check_batch(self, F, "trace statistics")
         with torch.cuda.device(self.device):
             S = F.shape[0]
             t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))

@@ -462,59 +462,27 @@ class Inversion:
         with the 10 / 50 / 90 % quantiles over the realisations, with voxel_probability `probability` (C, yN, xN, zN) (or the block
         shape) = the fraction of realisations in which the voxel passes, with approximate `clipped_fraction`.  write=True:
         grade_tonnage.csv in outpath."""
-        from . import blocksupport, resources
-        s = self.settings
-        p = resources.property_index(prop)
-        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
-            raise RuntimeError("grade_tonnage() reduces realisations of the survey of cubing(): call cubing() first")
-        scale = [float(v) for v in self._cube_scale]
-        bounds = {resources.property_index(k): float(v) for k, v in (require or {}).items()}
-        if p in bounds:
-            raise ValueError("require names the other properties: %r is the one the cutoffs apply to" % (prop,))
-        if self.drillfield.size == 0 and (p == 2 or 2 in bounds):
-            raise ValueError("the drill cubes are NaN without drill data: no cutoff on them")
-        lo = np.full(3, -np.inf)
-        for q, v in bounds.items():
-            if np.isnan(v):
-                raise ValueError("a lower bound of require is NaN")
-            lo[q] = v / scale[q]
-        cut = np.asarray(cutoffs, dtype=np.float64).reshape(-1)
-        t, order = resources.normalised_thresholds(cut, offset, self._cube_scale[p])
-        grid = (s.yNcube, s.xNcube, s.zNcube)
-        box, shape = None, grid
-        if block is not None:
-            bx, by, bz = blocksupport.check_box(block, (s.xNcube, s.yNcube, s.zNcube))
-            box = (by, bx, bz)
-            shape = blocksupport.block_counts(grid, box)
-        n, start = int(n), int(start)
-        if n < 1 or start < 0:
-            raise ValueError("n >= 1 realisations from start >= 0, got n = %r, start = %r" % (n, start))
+        from . import resources
+        q = self._cutoff_query("grade_tonnage() reduces realisations of the survey of cubing()", prop, cutoffs, offset, require, block, region,
+                               n, start)
         eng = self.engine
-        mask = None
-        if region is not None:
-            region = np.asarray(region)
-            if region.dtype != np.bool_ or region.shape != tuple(shape):
-                raise ValueError("region must be a boolean array of shape %r, got %r %r" % (tuple(shape), region.dtype, region.shape))
-            mask = torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=eng.device)
-        nel = int(np.prod(shape))
-        hits = torch.zeros((t.size, nel), dtype=torch.int32, device=eng.device) if voxel_probability else None
+        mask = self._on_device(q.mask)
+        hits = torch.zeros((q.t.size, int(np.prod(q.shape))), dtype=torch.int32, device=eng.device) if voxel_probability else None
         cnts, sums = [], []
-        for fp, _, _ in self._posterior_batches(n, seed, start, approximate, batch):
-            c, v = eng.cutoff_statistics(fp, p, t, lo=lo, mask=mask, box=box, hits=hits)
+        for fp, _, _ in self._posterior_batches(q.n, seed, q.start, approximate, batch):
+            c, v = eng.cutoff_statistics(fp, q.p, q.t, lo=q.lo, mask=mask, box=q.box, hits=hits)
             cnts.append(c)
             sums.append(v)
-        count = resources.caller_order(torch.cat(cnts).cpu().numpy(), order)
-        total = resources.caller_order(torch.cat(sums).cpu().numpy(), order)
-        out = dict(cutoffs=cut.copy())
-        out.update(resources.tonnage_tables(count, total, scale[p], offset, float(s.xvoxsize) * float(s.yvoxsize) * float(s.zvoxsize)))
+        out = dict(cutoffs=q.cut.copy())
+        out.update(resources.tonnage_tables(torch.cat(cnts).cpu().numpy()[:, q.inverse], torch.cat(sums).cpu().numpy()[:, q.inverse],
+                                            q.scale[q.p], offset, self._voxel_volume()))
         if voxel_probability:
-            prob = hits.cpu().numpy().astype(np.float64) / n
-            out["probability"] = resources.caller_order(prob.T, order).T.reshape((t.size,) + tuple(shape))
+            out["probability"] = self._probability(hits, q)
         if approximate:
             out["clipped_fraction"] = self._sampler_cache[1].clipped_fraction
         if write:
             import os
-            resources.curve_frame(out).to_csv(os.path.join(s.outpath, "grade_tonnage.csv"), index=False)
+            resources.curve_frame(out).to_csv(os.path.join(self.settings.outpath, "grade_tonnage.csv"), index=False)
         return out
 
     def exceedance_probability(self, cutoffs, prop="drill", offset=0.0):
@@ -549,65 +517,35 @@ class Inversion:
         the realisations, `probability_largest` / `probability_seeded` (C, yN, xN, zN) (or the block shape) = the fraction of
         realisations in which the voxel lies in that body, and with approximate `clipped_fraction`.  write=True: geobodies.csv in
         outpath."""
-        from . import blocksupport, geobodies as gb, resources
+        from . import geobodies as gb
         s = self.settings
-        p = resources.property_index(prop)
-        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
-            raise RuntimeError("geobodies() labels realisations of the survey of cubing(): call cubing() first")
+        q = self._cutoff_query("geobodies() labels realisations of the survey of cubing()", prop, cutoffs, offset, require, block, region, n, start)
         neighbours = gb.check_neighbours(neighbours)
         want_l, want_s = gb.check_probability(probability)
-        scale = [float(v) for v in self._cube_scale]
-        bounds = {resources.property_index(k): float(v) for k, v in (require or {}).items()}
-        if p in bounds:
-            raise ValueError("require names the other properties: %r is the one the cutoffs apply to" % (prop,))
-        if self.drillfield.size == 0 and (p == 2 or 2 in bounds):
-            raise ValueError("the drill cubes are NaN without drill data: no cutoff on them")
-        lo = np.full(3, -np.inf)
-        for q, v in bounds.items():
-            if np.isnan(v):
-                raise ValueError("a lower bound of require is NaN")
-            lo[q] = v / scale[q]
-        cut = np.asarray(cutoffs, dtype=np.float64).reshape(-1)
-        t, order = resources.normalised_thresholds(cut, offset, self._cube_scale[p])
         grid = (s.yNcube, s.xNcube, s.zNcube)
         sd = gb.parse_seeds(seeds, grid, drill=self._drill_selection() if isinstance(seeds, str) and seeds == "drill" else None)
-        box, shape = None, grid
-        if block is not None:
-            bx, by, bz = blocksupport.check_box(block, (s.xNcube, s.yNcube, s.zNcube))
-            box = (by, bx, bz)
-            shape = blocksupport.block_counts(grid, box)
-            sd = gb.seeds_to_blocks(sd, grid, box)
-        n, start, min_voxels = int(n), int(start), int(min_voxels)
-        if n < 1 or start < 0:
-            raise ValueError("n >= 1 realisations from start >= 0, got n = %r, start = %r" % (n, start))
+        if q.box is not None:
+            sd = gb.seeds_to_blocks(sd, grid, q.box)
+        min_voxels = int(min_voxels)
         if min_voxels < 1:
             raise ValueError("min_voxels >= 1, got %r" % (min_voxels,))
         eng = self.engine
-        mask = None
-        if region is not None:
-            region = np.asarray(region)
-            if region.dtype != np.bool_ or region.shape != tuple(shape):
-                raise ValueError("region must be a boolean array of shape %r, got %r %r" % (tuple(shape), region.dtype, region.shape))
-            mask = torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=eng.device)
-        nel = int(np.prod(shape))
-        hits_l = torch.zeros((t.size, nel), dtype=torch.int32, device=eng.device) if want_l else None
-        hits_s = torch.zeros((t.size, nel), dtype=torch.int32, device=eng.device) if want_s else None
+        mask = self._on_device(q.mask)
+        nel = int(np.prod(q.shape))
+        hits_l = torch.zeros((q.t.size, nel), dtype=torch.int32, device=eng.device) if want_l else None
+        hits_s = torch.zeros((q.t.size, nel), dtype=torch.int32, device=eng.device) if want_s else None
         stats, sums = [], []
-        for fp, _, _ in self._posterior_batches(n, seed, start, approximate, batch):
-            st, sm = eng.body_statistics(fp, p, t, lo=lo, mask=mask, box=box, neighbours=neighbours, min_count=min_voxels, seeds=sd,
+        for fp, _, _ in self._posterior_batches(q.n, seed, q.start, approximate, batch):
+            st, sm = eng.body_statistics(fp, q.p, q.t, lo=q.lo, mask=mask, box=q.box, neighbours=neighbours, min_count=min_voxels, seeds=sd,
                                          hits_largest=hits_l, hits_seeded=hits_s)
             stats.append(st)
             sums.append(sm)
-        inv_order = np.empty_like(order)
-        inv_order[order] = np.arange(order.size)
-        stats = torch.cat(stats).cpu().numpy()[:, inv_order]
-        sums = torch.cat(sums).cpu().numpy()[:, inv_order]
-        out = dict(cutoffs=cut.copy())
-        out.update(gb.body_tables(stats, sums, scale[p], offset, float(s.xvoxsize) * float(s.yvoxsize) * float(s.zvoxsize)))
+        out = dict(cutoffs=q.cut.copy())
+        out.update(gb.body_tables(torch.cat(stats).cpu().numpy()[:, q.inverse], torch.cat(sums).cpu().numpy()[:, q.inverse], q.scale[q.p], offset,
+                                  self._voxel_volume()))
         for name, hits in (("probability_largest", hits_l), ("probability_seeded", hits_s)):
             if hits is not None:
-                prob = hits.cpu().numpy().astype(np.float64) / n
-                out[name] = prob[inv_order].reshape((t.size,) + tuple(shape))
+                out[name] = self._probability(hits, q)
         if approximate:
             out["clipped_fraction"] = self._sampler_cache[1].clipped_fraction
         if write:
@@ -621,38 +559,54 @@ class Inversion:
         index and 0 outside (the numbering of scipy.ndimage.label), sizes (B,) the voxels of each.  NaN is outside; region: a
         boolean cube restricting the voxels."""
         from . import geobodies as gb
+        neighbours = gb.check_neighbours(neighbours)
+        grid, F, cutoff, mask = self._cube_query(cube, cutoff, region)
+        labels = torch.empty((1, 1, F.shape[2]), dtype=torch.int32, device=F.device)
+        self.engine.body_statistics(F, 0, cutoff, mask=mask, neighbours=neighbours, labels=labels)
+        numbered, sizes = gb.renumber(labels.cpu().numpy().reshape(grid))
+        return numbered, sizes
+
+    # ---- what grade_tonnage(), geobodies() and drill_intercepts() share -----------------------------------------------------------
+    def _cutoff_query(self, what, prop, cutoffs, offset, require, block, region, n, start):
+        """resources.cutoff_query for the survey of cubing(); `what` opens the sentence that asks for cubing() first."""
+        from . import resources
+        resources.property_index(prop)                            # (first, as before: a bad property is a ValueError even before cubing())
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("%s: call cubing() first" % what)
+        s = self.settings
+        return resources.cutoff_query(prop, cutoffs, offset, require, self._cube_scale, self.drillfield.size > 0, (s.yNcube, s.xNcube, s.zNcube),
+                                      block, region, n, start)
+
+    def _on_device(self, mask):
+        """A host mask vector (or None) on the engine's device."""
+        return None if mask is None else torch.as_tensor(mask, device=self.engine.device)
+
+    def _voxel_volume(self):
+        s = self.settings
+        return float(s.xvoxsize) * float(s.yvoxsize) * float(s.zvoxsize)
+
+    def _probability(self, hits, q):
+        """(C, n) device counts over the q.n realisations -> the fractions in the caller's cutoff order, (C,) + q.shape."""
+        return (hits.cpu().numpy().astype(np.float64) / q.n)[q.inverse].reshape((q.t.size,) + tuple(q.shape))
+
+    def _cube_query(self, cube, cutoff, region):
+        """One (yN, xN, zN) cube and one cutoff, for label_bodies() and column_intercepts(), as the engine's statistics take them:
+        (grid, F (1, 3, N) device batch whose property 0 holds the cube, [cutoff], mask on the device or None), checked first."""
+        from . import resources
         s = self.settings
         grid = (s.yNcube, s.xNcube, s.zNcube)
-        neighbours = gb.check_neighbours(neighbours)
         cube = np.asarray(cube, dtype=np.float64)
         if cube.shape != grid:
             raise ValueError("cube must have the shape %r, got %r" % (grid, cube.shape))
         cutoff = float(cutoff)
         if np.isnan(cutoff):
             raise ValueError("the cutoff is NaN")
-        eng = self.engine
-        N = cube.size
-        mask = None
-        if region is not None:
-            region = np.asarray(region)
-            if region.dtype != np.bool_ or region.shape != grid:
-                raise ValueError("region must be a boolean array of shape %r, got %r %r" % (grid, region.dtype, region.shape))
-            mask = torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=eng.device)
-        F = torch.zeros((1, 3, N), dtype=torch.float64, device=eng.device)
-        F[0, 0] = torch.as_tensor(cube.reshape(-1).copy(), device=eng.device)
-        labels = torch.empty((1, 1, N), dtype=torch.int32, device=eng.device)
-        eng.body_statistics(F, 0, [cutoff], mask=mask, neighbours=neighbours, labels=labels)
-        numbered, sizes = gb.renumber(labels.cpu().numpy().reshape(grid))
-        return numbered, sizes
+        mask = self._on_device(resources.region_mask(region, grid))
+        F = torch.zeros((1, 3, cube.size), dtype=torch.float64, device=self.engine.device)
+        F[0, 0] = torch.as_tensor(cube.reshape(-1).copy(), device=F.device)
+        return grid, F, [cutoff], mask
 
     # ---- drill-intercept statistics (DESIGN.md section 19) ------------------------------------------------------------------------
-    def _region_mask(self, region, shape):
-        if region is None:
-            return None
-        region = np.asarray(region)
-        if region.dtype != np.bool_ or region.shape != tuple(shape):
-            raise ValueError("region must be a boolean array of shape %r, got %r %r" % (tuple(shape), region.dtype, region.shape))
-        return torch.as_tensor(np.ascontiguousarray(region.reshape(-1)).astype(np.uint8), device=self.engine.device)
 
     def drill_intercepts(self, cutoffs, prop="drill", n=256, seed=0, start=0, batch=64, offset=0.0, require=None, region=None,
                          min_length=None, max_gap=0.0, holes=None, paths=None, step=None, approximate=False, write=False):
@@ -681,34 +635,17 @@ class Inversion:
         Always: `sample_length` (m) and the converted `min_len` and `max_gap_samples`.
         write=True: intercepts.csv and intercept_maps.csv (columns) or hole_intercepts.csv (holes, paths) in outpath.
         Block support, several ranks and a campaign utility built on these probabilities are out of scope."""
-        from . import hip, intercepts as ic, resources
+        from . import hip, intercepts as ic
         s = self.settings
-        p = resources.property_index(prop)
-        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
-            raise RuntimeError("drill_intercepts() reduces realisations of the survey of cubing(): call cubing() first")
-        scale = [float(v) for v in self._cube_scale]
-        bounds = {resources.property_index(k): float(v) for k, v in (require or {}).items()}
-        if p in bounds:
-            raise ValueError("require names the other properties: %r is the one the cutoffs apply to" % (prop,))
-        if self.drillfield.size == 0 and (p == 2 or 2 in bounds):
-            raise ValueError("the drill cubes are NaN without drill data: no cutoff on them")
+        q = self._cutoff_query("drill_intercepts() reduces realisations of the survey of cubing()", prop, cutoffs, offset, require, None, region,
+                               n, start)
         if holes is not None and paths is not None:
             raise ValueError("give holes or paths, not both")
-        lo = np.full(3, -np.inf)
-        for q, v in bounds.items():
-            if np.isnan(v):
-                raise ValueError("a lower bound of require is NaN")
-            lo[q] = v / scale[q]
-        cut = np.asarray(cutoffs, dtype=np.float64).reshape(-1)
-        t, order = resources.normalised_thresholds(cut, offset, self._cube_scale[p])
-        grid = (s.yNcube, s.xNcube, s.zNcube)
-        n, start = int(n), int(start)
-        if n < 1 or start < 0:
-            raise ValueError("n >= 1 realisations from start >= 0, got n = %r, start = %r" % (n, start))
+        grid = q.shape
         eng = self.engine
         if eng.world > 1:
             raise NotImplementedError("drill intercepts run on one rank (world = %d)" % eng.world)
-        mask = self._region_mask(region, grid)
+        mask = self._on_device(q.mask)
         dz, csr = float(s.zvoxsize), None
         if holes is not None:
             csr = ic.hole_traces(holes, grid)
@@ -718,10 +655,10 @@ class Inversion:
         min_len, gap = ic.samples_of(min_length, max_gap, dz)
         traces = None if csr is None else hip.TraceSet(csr[0], csr[1], eng.N, device=eng.device)
         K, Lmax = (grid[0] * grid[1], grid[2]) if traces is None else (traces.K, traces.Lmax)
-        maps = hip.trace_maps(t.size, K, Lmax, device=eng.device)
+        maps = hip.trace_maps(q.t.size, K, Lmax, device=eng.device)
         tabs, dets, dsms = [], [], []
-        for fp, _, _ in self._posterior_batches(n, seed, start, approximate, batch):
-            r = eng.trace_statistics(fp, p, t, lo=lo, mask=mask, traces=traces, min_len=min_len, max_gap=gap, maps=maps,
+        for fp, _, _ in self._posterior_batches(q.n, seed, q.start, approximate, batch):
+            r = eng.trace_statistics(fp, q.p, q.t, lo=q.lo, mask=mask, traces=traces, min_len=min_len, max_gap=gap, maps=maps,
                                      detail=traces is not None)
             if traces is None:
                 tabs.append(r)
@@ -729,19 +666,17 @@ class Inversion:
                 tabs.append(r[0])
                 dets.append(r[1].cpu())
                 dsms.append(r[2].cpu())
-        inv_order = np.empty_like(order)
-        inv_order[order] = np.arange(order.size)
-        out = dict(cutoffs=cut.copy(), sample_length=dz, min_len=min_len, max_gap_samples=gap)
-        out.update(ic.intercept_tables(torch.cat(tabs).cpu().numpy()[:, inv_order], dz,
+        out = dict(cutoffs=q.cut.copy(), sample_length=dz, min_len=min_len, max_gap_samples=gap)
+        out.update(ic.intercept_tables(torch.cat(tabs).cpu().numpy()[:, q.inverse], dz,
                                        float(s.xvoxsize) * float(s.yvoxsize) if traces is None else None))
-        host = {k: v.cpu().numpy()[inv_order] for k, v in maps.items()}
-        summary = ic.intercept_maps(host, n, scale[p], offset, dz)
+        host = {k: v.cpu().numpy()[q.inverse] for k, v in maps.items()}
+        summary = ic.intercept_maps(host, q.n, q.scale[q.p], offset, dz)
         if traces is None:
-            shape = (t.size, grid[0], grid[1])
-            summary = {k: ({q: a.reshape(shape) for q, a in v.items()} if isinstance(v, dict) else v.reshape(shape)) for k, v in summary.items()}
+            shape = (q.t.size, grid[0], grid[1])
+            summary = {k: ({name: a.reshape(shape) for name, a in v.items()} if isinstance(v, dict) else v.reshape(shape)) for k, v in summary.items()}
         out.update(summary)
         if traces is not None:
-            out["per_realisation"] = ic.per_realisation(torch.cat(dets).numpy()[:, inv_order], torch.cat(dsms).numpy()[:, inv_order], scale[p],
+            out["per_realisation"] = ic.per_realisation(torch.cat(dets).numpy()[:, q.inverse], torch.cat(dsms).numpy()[:, q.inverse], q.scale[q.p],
                                                         offset, dz)
             out["trace_lengths"] = traces.lengths.copy()
         if approximate:
@@ -765,19 +700,9 @@ class Inversion:
         one), `mean_value` = its mean with the composited waste (NaN without one), `n_intercepts` (of at least min_length)."""
         from . import intercepts as ic
         s = self.settings
-        grid = (s.yNcube, s.xNcube, s.zNcube)
-        cube = np.asarray(cube, dtype=np.float64)
-        if cube.shape != grid:
-            raise ValueError("cube must have the shape %r, got %r" % (grid, cube.shape))
-        cutoff = float(cutoff)
-        if np.isnan(cutoff):
-            raise ValueError("the cutoff is NaN")
         min_len, gap = ic.samples_of(min_length, max_gap, s.zvoxsize)
-        eng = self.engine
-        mask = self._region_mask(region, grid)
-        F = torch.zeros((1, 3, cube.size), dtype=torch.float64, device=eng.device)
-        F[0, 0] = torch.as_tensor(cube.reshape(-1).copy(), device=eng.device)
-        _, det, dsm = eng.trace_statistics(F, 0, [cutoff], mask=mask, min_len=min_len, max_gap=gap, detail=True)
+        grid, F, cutoff, mask = self._cube_query(cube, cutoff, region)
+        _, det, dsm = self.engine.trace_statistics(F, 0, cutoff, mask=mask, min_len=min_len, max_gap=gap, detail=True)
         r = ic.per_realisation(det.cpu().numpy(), dsm.cpu().numpy(), 1.0, 0.0, s.zvoxsize)
         shape = (grid[0], grid[1])
         return {"thickness": r["thickness"].reshape(shape), "depth_to_top": r["depth_to_top"].reshape(shape), "from": r["from"].reshape(shape),

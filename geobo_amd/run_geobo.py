@@ -65,6 +65,12 @@ def run(settings, method="auto", bayesopt=True, write=True):
             for c, n in zip(samples, ("density", "magsus", "drill")):
                 for k in range(nsamp):
                     dataio.create_vtkcube(c[k], origin, voxelsize, fname=os.path.join(s.outpath, "cube_%s_sample_%03d.vtk" % (n, k)))
+    def write_probability_cubes(cubes_p, prop, blk, tag):
+        """One VTK cube per cutoff, cube_<property>_<tag>_<k>.vtk, at voxel or block support; nothing for None."""
+        from .resources import PROPS, property_index
+        size = voxelsize if blk is None else tuple(v * b for v, b in zip(voxelsize, blk))
+        for k, cube in enumerate(cubes_p if cubes_p is not None else ()):
+            dataio.create_vtkcube(cube, origin, size, fname=os.path.join(s.outpath, "cube_%s_%s_%d.vtk" % (PROPS[property_index(prop)], tag, k)))
     gt = getattr(s, "grade_tonnage", None)                # optional YAML key grade_tonnage: {cutoffs, property, samples, offset, block,
     if gt:                                                # voxel_probability}; sample_seed is shared with posterior_samples
         prop = gt.get("property", "drill")
@@ -74,10 +80,7 @@ def run(settings, method="auto", bayesopt=True, write=True):
                                 write=write)
         out["grade_tonnage"] = res
         if write and "probability" in res:
-            from .resources import PROPS, property_index
-            size = voxelsize if blk is None else tuple(v * b for v, b in zip(voxelsize, blk))
-            for k, cube in enumerate(res["probability"]):
-                dataio.create_vtkcube(cube, origin, size, fname=os.path.join(s.outpath, "cube_%s_exceed_%d.vtk" % (PROPS[property_index(prop)], k)))
+            write_probability_cubes(res["probability"], prop, blk, "exceed")
     gbd = getattr(s, "geobodies", None)                   # optional YAML key geobodies: {cutoffs, property, samples, offset, block,
     if gbd:                                               # neighbours, min_voxels, seeds: drill, probability}; sample_seed is shared
         prop = gbd.get("property", "drill")
@@ -88,12 +91,8 @@ def run(settings, method="auto", bayesopt=True, write=True):
                             probability=gbd.get("probability") or None, write=write)
         out["geobodies"] = res
         if write:
-            from .resources import PROPS, property_index
-            size = voxelsize if blk is None else tuple(v * b for v, b in zip(voxelsize, blk))
             # (one cube per cutoff: the seeded body's probability when asked for, else the largest body's)
-            cubes_p = res.get("probability_seeded", res.get("probability_largest"))
-            for k, cube in enumerate(cubes_p if cubes_p is not None else ()):
-                dataio.create_vtkcube(cube, origin, size, fname=os.path.join(s.outpath, "cube_%s_connected_%d.vtk" % (PROPS[property_index(prop)], k)))
+            write_probability_cubes(res.get("probability_seeded", res.get("probability_largest")), prop, blk, "connected")
     dri = getattr(s, "drill_intercepts", None)            # optional YAML key drill_intercepts: {cutoffs, property, samples, offset,
     if dri:                                               # min_length, max_gap} (metres), optionally holes or paths (+ step)
         from .intercepts import parse_yaml
