@@ -67,6 +67,11 @@ def _chk(t, name, dtype=F64):
     return t
 
 
+def _ptrs(ts, name):
+    """The device pointers of the fp64 tensors `ts` as a C array of void*."""
+    return (C.c_void_p * len(ts))(*[_chk(t, name).data_ptr() for t in ts])
+
+
 def _rowmajor(t, name):
     _chk(t, name)
     if t.dim() != 2 or t.stride(1) != 1:
@@ -646,9 +651,7 @@ def toeplitz_y(ny, C, R, src, tabs, outs, y0=0, y1=None, plane=None, accumulate=
     y1 = ny if y1 is None else y1
     n = len(tabs)
     assert 1 <= n <= 3 and len(outs) == n
-    import ctypes                    # (the argument C -- modes per plane -- shadows the module alias here)
-    tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in (_chk(t, "tab") for t in tabs)])
-    op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in (_chk(o, "out") for o in outs)])
+    tp, op = _ptrs(tabs, "tab"), _ptrs(outs, "out")
     fn, name = (lib.geobo_toeplitz_y3_add, "geobo_toeplitz_y3_add") if accumulate else (lib.geobo_toeplitz_y3, "geobo_toeplitz_y3")
     _lib.check(fn(int(ny), int(C), int(C if plane is None else plane), int(R), n, _p(_chk(src, "src")), tp, op, int(y0), int(y1), _stream()), name)
 
@@ -702,9 +705,7 @@ def spectral_y(ny, C, R, src, tabs, outs, y0=0, y1=None, plane=None, accumulate=
     y1 = ny if y1 is None else y1
     n = len(tabs)
     assert 1 <= n <= 3 and len(outs) == n
-    import ctypes
-    tp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in (_chk(t, "tab") for t in tabs)])
-    op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in (_chk(o, "out") for o in outs)])
+    tp, op = _ptrs(tabs, "tab"), _ptrs(outs, "out")
     _lib.check(lib.geobo_spectral_y3(int(ny), int(C), int(C if plane is None else plane), int(R), n, _p(_chk(src, "src")), tp, op, int(y0), int(y1),
                                      1 if accumulate else 0, _p(spectral_y_basis(ny, src.device)), _stream()), "geobo_spectral_y3")
 
@@ -738,10 +739,8 @@ def spectral_y3t(ny, C, R, src_g, src_m, tabs_g, tabs_m, outs, plane=None):
     lib = require_gpu()
     n = len(outs)
     assert 1 <= n <= 3 and len(tabs_g) == n and len(tabs_m) == n
-    import ctypes
-    arr = lambda ts, what: (ctypes.c_void_p * n)(*[t.data_ptr() for t in (_chk(t, what) for t in ts)])
     _lib.check(lib.geobo_spectral_y3t(int(ny), int(C), int(C if plane is None else plane), int(R), n, _p(_chk(src_g, "src_g")), _p(_chk(src_m, "src_m")),
-                                      arr(tabs_g, "tab"), arr(tabs_m, "tab"), arr(outs, "out"), _p(spectral_y_basis(ny, src_g.device)), _stream()),
+                                      _ptrs(tabs_g, "tab"), _ptrs(tabs_m, "tab"), _ptrs(outs, "out"), _p(spectral_y_basis(ny, src_g.device)), _stream()),
                "geobo_spectral_y3t")
 
 

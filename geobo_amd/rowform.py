@@ -172,15 +172,7 @@ class RowFormMixin:
         zx = gram.zx_supported() and sp.fused_ss()           # rows of Z as [iy][iz][ix]: what the fused (row, z)-plane inverse writes
         zc = min(self._rows_chunk(2), (rows_r + sp.R - 1) // sp.R * sp.R)
         Zg, Zm = self._workspace2d("Zg", zc, N), self._workspace2d("Zm", zc, N)
-        slots = sp.ss_slots()
-        ss = [self._workspace("post_ss_%d" % jj, (slots, ny, nx * nz)) for jj in range(P_c)]
-        for t in ss:
-            t.zero_()
-        gens_g, gens_m = [step.gens[(0, j)] for j in props], [step.gens[(1, j)] for j in props]
-        swap = (lambda g: g.view(ny, sp.Px, sp.Pz).transpose(1, 2).contiguous().view(-1)) if zx else (lambda g: g)
-        tg, tm = [swap(g) for g in gens_g], [swap(g) for g in gens_m]
-        # blocks (0, 1) and (1, 0) of a symmetric prior coincide: three y-stage products per two-term row instead of four
-        y2s = sp.y2s_tables(tg, tm) if tuple(props[:2]) == (0, 1) else None
+        ss, tg, tm, y2s, voxel_order = self._ss_cubes(step, zx)
         fl_z = gram.flops(1, ny) + 2 * 3 * 2.0 * 128 * 128 * 64
         for two in (False, True):
             for c0 in range(0, rows_r, zc):
@@ -197,10 +189,7 @@ class RowFormMixin:
                             lambda: sp.reduce_ss(Zg, n, tg, Zm if two else None, 0, tm, ss, y2s=y2s),
                             valu=sp.valu_ss(0 if two else n, n if two else 0, P_c, shared))
         for jj, t in enumerate(ss):
-            if zx:
-                ssq[jj].copy_(t.sum(0).view(ny, nz, nx).transpose(1, 2).reshape(-1))
-            else:
-                ssq[jj].copy_(t.sum(0).reshape(-1))
+            ssq[jj].copy_(voxel_order(t))
         # the rows behind the sensor rows (only they see the drill columns of L^-1): an equal share per rank
         dper = -(-Md // G)
         d0 = min(Md, r * dper)

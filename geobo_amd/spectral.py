@@ -196,7 +196,7 @@ def pool_distinct_planes(ny, jy, jx):
 
 class PooledRows:
     """Operator rows of a lattice survey as windows of the pool of distinct plane SPECTRA (SpectralProduct.plane_pool): the y stage reads
-    them in place (hip.spectral_y_lattice), no forward transform per row.  pool: [nx][2ny-3][Cp] then the boundary planes [Ms][2][Cp]
+    them in place (geobo_spectral_y_lattice), no forward transform per row.  pool: [nx][2ny-3][Cp] then the boundary planes [Ms][2][Cp]
     (`edge`, a view of the same buffer); row_off: int64 device offsets of the windows; jy / jx: host lattice indices (sweep order)."""
 
     def __init__(self, pool, row_off, edge, jy, jx, r0=0, geo=None):
@@ -295,9 +295,9 @@ class SpectralProduct:
         rows.row_off = row_off
         return rows
 
-    def _pool_batch(self, A, r0, R):
-        """(device int32 sweep order, distinct planes) of the rows r0 .. r0 + R of a pooled operator (constants of the survey: kept)."""
-        a = A.r0 + r0
+    def _pool_batch(self, A, R):
+        """(device int32 sweep order, distinct planes) of the first R rows of a pooled operator (constants of the survey: kept)."""
+        a = A.r0
         key = (A.geo, a, R)
         hit = self._pool_tabs.get(key)
         if hit is None:
@@ -305,12 +305,12 @@ class SpectralProduct:
             hit = self._pool_tabs[key] = (torch.from_numpy(pool_order(jy, jx)).to(self.device), pool_distinct_planes(self.ny, jy, jx))
         return hit
 
-    def _ystage_pooled(self, A, r0, R, tabs, outs, y0, y1):
-        """The y stage of the rows r0 .. r0 + R of a pooled operator, in place from the pool.  Algorithmic bytes for the per-kernel
+    def _ystage_pooled(self, A, R, tabs, outs, y0, y1):
+        """The y stage of the first R rows of a pooled operator, in place from the pool.  Algorithmic bytes for the per-kernel
         roofline: every distinct plane of the batch once + the output slabs."""
         ny, C, Cp = self.ny, self.Px * self.Pz, self.Cp
-        order, distinct = self._pool_batch(A, r0, R)
-        a = A.r0 + r0
+        order, distinct = self._pool_batch(A, R)
+        a = A.r0
         fn = lambda: hip.spectral_y_lattice(ny, C, R, A.pool, A.row_off[a:], A.edge[a * 2 * Cp:], 2 * Cp, order, tabs, outs, y0, y1, plane=Cp)
         name = "kernel:toeplitz_y" if len(tabs) >= 2 else "kernel:toeplitz_y_single"
         return self._launch(name, 8.0 * C * (distinct + R * len(tabs) * (y1 - y0)), R, self.y_stage_flop(1, len(tabs), y1 - y0), fn)
@@ -320,9 +320,10 @@ class SpectralProduct:
     y_mfma = property(lambda self: self.forms.y == "mfma")
     fused_xz = property(lambda self: self.forms.xz in ("fold", "fused"))     # x and z of one whole plane inside one kernel (radix-2 or plain)
 
-    def _ystage(self, ny, C, R, src, tabs, outs, y0, y1, plane, accumulate=False):
+    def _ystage(self, R, src, tabs, outs, y0, y1, accumulate=False):
         """geobo_toeplitz_y launch, bracketed for the bench's per-kernel roofline when a timer is set: algorithmic bytes = the rows'
         (x, z)-spectrum read once + one output slab per property block (read as well when the launch accumulates)."""
+        ny, C, plane = self.ny, self.Px * self.Pz, self.Cp
         # (the long-axis matrix-pipe kernel computes every output of a row whatever the slab; the windowed direct kernel only the chunks of
         # 16 that cover it: narrow slabs -- the y-slab shards of the column form -- stay with the direct kernel: 0.55 against 1.33 ms for 16
         # of 128 planes)
@@ -339,6 +340,77 @@ class SpectralProduct:
         if self.kernel_timer is None:
             return fn()
         return self.kernel_timer(name, nbytes, fn, valu=rows * flop[1], flop=rows * flop[0])
+
+    def _join(self, specs, gens, R, ylo, yhi, y2s=None, squaring=False):
+        """The y stage of R rows for one group of property blocks: THE place that picks its kernel, timer name, bytes and flop.
+        specs: one (x, z)-spectrum per term (work buffers of forward_zx; the PooledRows themselves where the rows' spectra are windows of
+        the pool); gens[t][i]: generator of term t for block i of the group; y2s: the (D0, X, D1) tables of y2s_tables() when this group is
+        their pair; squaring: the outputs feed the squaring inverse transform.  Returns (outs, outs2): one spectrum per block over the
+        slab [ylo, yhi) in S / S1 / S2, and the second term's spectra in Sb / S1b where the terms do not meet here (y_two_term
+        "separate", the odd last block of "y2t") -- [] where there are none, None where a block pair met in ONE pass."""
+        ny, C, Cp, meet = self.ny, self.Px * self.Pz, self.Cp, self.forms.y_two_term
+        nb = len(gens[0])
+        outs = [self.buf(("S", "S1", "S2")[i], R * (yhi - ylo) * Cp) for i in range(nb)]
+        if isinstance(specs[0], PooledRows):
+            for i in range(0, nb, 2):       # (two blocks + one, each its own launch with its own bytes: what geobo_spectral_y3 does inside one call)
+                self._ystage_pooled(specs[0], R, gens[0][i:i + 2], outs[i:i + 2], ylo, yhi)
+            return outs, []
+        if len(specs) == 1:
+            self._ystage(R, specs[0], gens[0], outs, ylo, yhi)
+            return outs, []
+        assert (ylo, yhi) == (0, ny)
+        (sg, sm), (gg, gm) = specs, gens
+        # inherited, unmeasured: the squaring inverse is fed by two accumulating launches where the storing one takes geobo_spectral_y3t
+        y3t = self.forms.y3t and not squaring
+        if meet == "y2t" and nb == 2:
+            # both terms in ONE pass: with the shared cross block three products per mode (geobo_toeplitz_y2s), otherwise four
+            if y2s is not None:
+                y2s_fn = hip.spectral_y2s if self.y_mfma else hip.toeplitz_y2s
+                name, fn = "kernel:toeplitz_y2s", lambda: y2s_fn(ny, C, R, sg, sm, y2s[0], y2s[1], y2s[2], outs, plane=Cp)
+            else:
+                name, fn = "kernel:toeplitz_y2t", lambda: hip.toeplitz_y2t(ny, C, R, sg, sm, gg, gm, outs, plane=Cp)
+            self._launch(name, 8.0 * R * C * 4 * ny, R, self.y_stage_flop(2, 2, shared=y2s is not None), fn)
+            return outs, None
+        if meet == "add" and y3t:
+            # the terms meet in the y spectrum: 2 + nb transforms instead of 2 (1 + nb), no read-modify-write of the outputs
+            fn = lambda: hip.spectral_y3t(ny, C, R, sg, sm, gg, gm, outs, plane=Cp)
+            self._launch("kernel:toeplitz_y", 8.0 * R * C * ny * (2 + nb), R, self.y_stage_flop(2, nb), fn)
+            return outs, []
+        self._ystage(R, sg, gg, outs, ylo, yhi)
+        if meet == "add":                   # the second y stage adds into the first one's output: ONE inverse transform per block
+            self._ystage(R, sm, gm, outs, ylo, yhi, accumulate=True)
+            return outs, []
+        outs2 = [self.buf(("Sb", "S1b")[i], R * ny * Cp) for i in range(nb)]
+        self._ystage(R, sm, gm, outs2, ylo, yhi)
+        return outs, outs2
+
+    def _rows_spectrum(self, A, r0, R, out_name):
+        """(x, z)-spectrum of the rows r0 .. r0 + R of an operand: tensor rows, LatticeRows or PooledRows (nothing to transform)."""
+        if isinstance(A, PooledRows):
+            return A.rows(r0)
+        if isinstance(A, LatticeRows):
+            return self.forward_zx(A.rows(r0), R, self.G, out_name=out_name)
+        return self.forward_zx(A[r0:], R, self.G, src_row_stride=A.stride(0), out_name=out_name)
+
+    def _drive(self, batches, terms, sink, ylo, yhi, y2s=None, squaring=False):
+        """Every dense-y product: forward transform each term, join, sink.  batches: [(r0, R, nterms)]; terms: [(rows, index of their
+        first row, generators)]; sink(r0, R, js, outs, outs2) takes the joined spectra of the blocks js.  A sweep of the spectra feeds
+        2 blocks where a pair is joined in one pass or squared, otherwise 3."""
+        P_c = len(terms[0][2])
+        for r0, R, nt in batches:
+            specs = [self._rows_spectrum(A, r0 - first, R, name) for (A, first, _), name in zip(terms[:nt], ("T2", "T2b"))]
+            step = 2 if squaring or (nt == 2 and self.forms.y_two_term == "y2t") else 3
+            for j in range(0, P_c, step):
+                js = range(j, min(j + step, P_c))
+                tabs = y2s[1:] if y2s is not None and y2s[0] == j else None
+                sink(r0, R, js, *self._join(specs, [[g[jj] for jj in js] for _, _, g in terms[:nt]], R, ylo, yhi, tabs, squaring))
+
+    def _store(self, slabs, ylo, yhi):
+        """Sink: the storing inverse transform into rows r0 .. of every slab's targets."""
+        def sink(r0, R, js, outs, _):
+            for i, jj in enumerate(js):
+                self.backward_xz(outs[i], R, ylo, yhi, [(ya, yb, o[jj][r0:], o[jj].stride(0)) for ya, yb, o in slabs])
+        return sink
 
     def buf(self, name, n):
         b = self._bufs.get(name)
@@ -541,29 +613,10 @@ class SpectralProduct:
                     j += 1
 
     def _product_dense_y(self, A, Ms, gens, slabs):
-        """z and x through the spectrum, y as Toeplitz blocks: one read of the (x, z)-spectrum per pair of property blocks."""
-        ny, C, Cp = self.ny, self.Px * self.Pz, self.Cp
+        """z and x through the spectrum, y as Toeplitz blocks: one read of the (x, z)-spectrum per three property blocks."""
         ylo, yhi = min(s[0] for s in slabs), max(s[1] for s in slabs)
-        n_out = (yhi - ylo) * Cp
-        for r0 in range(0, Ms, self.R):
-            R = min(self.R, Ms - r0)
-            if isinstance(A, PooledRows):
-                t2 = None                                 # the rows' spectra are windows of the pool: nothing to transform
-            elif isinstance(A, LatticeRows):
-                t2 = self.forward_zx(A.rows(r0), R, self.G)
-            else:
-                t2 = self.forward_zx(A[r0:], R, self.G, src_row_stride=A.stride(0))
-            for j in range(0, len(gens), 3):              # up to three property blocks per read of the (x, z)-spectrum
-                js = list(range(j, min(j + 3, len(gens))))
-                u2 = [self.buf(("S", "S1", "S2")[i], R * n_out) for i in range(len(js))]
-                if t2 is None:
-                    # (two blocks + one, each its own launch with its own bytes: what hip.spectral_y does inside one call)
-                    for i in range(0, len(js), 2):
-                        self._ystage_pooled(A, r0, R, [gens[jj] for jj in js[i:i + 2]], u2[i:i + 2], ylo, yhi)
-                else:
-                    self._ystage(ny, C, R, t2, [gens[jj] for jj in js], u2, ylo, yhi, Cp)
-                for i, jj in enumerate(js):
-                    self.backward_xz(u2[i], R, ylo, yhi, [(ya, yb, o[jj][r0:], o[jj].stride(0)) for ya, yb, o in slabs])
+        batches = [(r0, min(self.R, Ms - r0), 1) for r0 in range(0, Ms, self.R)]
+        self._drive(batches, [(A, 0, gens)], self._store(slabs, ylo, yhi), ylo, yhi)
 
     # ---- posterior variance in the transposed order (engine._posterior_zpath) ------------------------------------------------------
     def fused_ss(self):
@@ -607,79 +660,36 @@ class SpectralProduct:
         (fused_ss): the storing product of every batch into a scratch of R rows, then geobo_sumsq_accum.
         y2s: tables of y2s_tables() for a pair of blocks whose cross blocks coincide -- the two-term rows of that pair then cost three
         y-stage products instead of four (geobo_toeplitz_y2s)."""
-        nx, ny, nz, C, Cp, R = self.nx, self.ny, self.nz, self.Px * self.Pz, self.Cp, self.R
-        P_c, y2s_tabs, meet = len(gens_g), y2s, self.forms.y_two_term     # meet: how the two terms of a row come together in the y stage
+        nx, ny, N, Cp, R = self.nx, self.ny, self.N, self.Cp, self.R
+        P_c = len(gens_g)
         if Zm is None:
             m_first = Mg
-        starts = list(range(0, min(m_first, Mg), R)) + list(range(m_first, Mg, R))
-        if not self.fused_ss():
-            N = self.N
-            add_y = self.dense_y and meet == "add"
-            for r0 in starts:
-                two = r0 >= m_first
-                Rb = min(R, (Mg if two else min(m_first, Mg)) - r0)
-                vg = [self.buf("SSV%d" % jj, R * N)[:R * N].view(R, N) for jj in range(P_c)]
-                if two and add_y:
-                    # both terms meet in the (x, z)-spectrum: the second y stage adds into the first one's output, ONE inverse
-                    # transform per block instead of two (what geobo_toeplitz_y2t does for the register-table kernel)
-                    t2g = self.forward_zx(Zg[r0:], Rb, self.G, src_row_stride=Zg.stride(0), out_name="T2")
-                    t2m = self.forward_zx(Zm[r0 - m_first:], Rb, self.G, src_row_stride=Zm.stride(0), out_name="T2b")
-                    for j in range(0, P_c, 3):
-                        js = list(range(j, min(j + 3, P_c)))
-                        u2 = [self.buf(("S", "S1", "S2")[i], Rb * ny * Cp) for i in range(len(js))]
-                        if self.forms.y3t:
-                            # both terms in ONE pass, meeting in the y spectrum (geobo_spectral_y3t): 2 + len(js) transforms instead of
-                            # 2 (1 + len(js)), no read-modify-write of the outputs
-                            fn = lambda: hip.spectral_y3t(ny, C, Rb, t2g, t2m, [gens_g[jj] for jj in js], [gens_m[jj] for jj in js], u2, plane=Cp)
-                            self._launch("kernel:toeplitz_y", 8.0 * Rb * C * ny * (2 + len(js)), Rb, self.y_stage_flop(2, len(js)), fn)
-                        else:
-                            self._ystage(ny, C, Rb, t2g, [gens_g[jj] for jj in js], u2, 0, ny, Cp)
-                            self._ystage(ny, C, Rb, t2m, [gens_m[jj] for jj in js], u2, 0, ny, Cp, accumulate=True)
-                        for i, jj in enumerate(js):
-                            self.backward_xz(u2[i], Rb, 0, ny, [(0, ny, vg[jj], vg[jj].stride(0))])
-                    for jj in range(P_c):
-                        hip.sumsq_accum(vg[jj], None, Rb, ss[jj].view(ss[jj].shape[0], -1))
-                    continue
+        one = min(m_first, Mg)
+        batches = [(r0, min(R, one - r0), 1) for r0 in range(0, one, R)] + [(r0, min(R, Mg - r0), 2) for r0 in range(m_first, Mg, R)]
+        if self.fused_ss():
+            def square(r0, Rb, js, outs, outs2):
+                for i, jj in enumerate(js):
+                    # (a pair joined in one pass -- outs2 None -- leaves the second input's row stride at its default; every other launch
+                    # states it, second input or not: the kernel reads it beside src2 only, the launch arguments stay what they were)
+                    second = {} if outs2 is None else dict(src2=outs2[i] if outs2 else None, in2_row=ny * Cp, r2_first=0)
+                    hip.xz2d_fold_inv_ss(nx, Rb, ny, outs[i], ny * Cp, Cp, self.F["x"], self.F["z"], ss[jj], **second)
+            return self._drive(batches, [(Zg, 0, gens_g), (Zm, m_first, gens_m)], square, 0, ny, y2s=y2s, squaring=True)
+        # The stored reduction joins the terms of a row only where the second accumulates into the first ("add").  "separate" has no
+        # join; "y2t" HAS one (product_two_term uses it on the same grids, 32 x 32 x 32 for one) and still runs two storing products
+        # here: inherited and unmeasured -- joining them is a performance change that wants its own measurement.
+        stored_join = self.dense_y and self.forms.y_two_term == "add"
+        for r0, Rb, nt in batches:
+            vg = [self.buf("SSV%d" % jj, R * N)[:R * N].view(R, N) for jj in range(P_c)]
+            vm = None
+            if nt == 2 and stored_join:
+                self._drive([(0, Rb, 2)], [(Zg[r0:], 0, gens_g), (Zm[r0 - m_first:], 0, gens_m)], self._store([(0, ny, vg)], 0, ny), 0, ny)
+            else:
                 self.product(Zg[r0:], Rb, gens_g, vg)
-                vm = None
-                if two:
+                if nt == 2:
                     vm = [self.buf("SSW%d" % jj, R * N)[:R * N].view(R, N) for jj in range(P_c)]
                     self.product(Zm[r0 - m_first:], Rb, gens_m, vm)
-                for jj in range(P_c):
-                    hip.sumsq_accum(vg[jj], vm[jj] if two else None, Rb, ss[jj].view(ss[jj].shape[0], -1))
-            return
-        for r0 in starts:
-            two = r0 >= m_first
-            Rb = min(R, (Mg if two else min(m_first, Mg)) - r0)
-            t2g = self.forward_zx(Zg[r0:], Rb, self.G, src_row_stride=Zg.stride(0), out_name="T2")
-            t2m = self.forward_zx(Zm[r0 - m_first:], Rb, self.G, src_row_stride=Zm.stride(0), out_name="T2b") if two else None
-            for j in range(0, P_c, 2):
-                js = list(range(j, min(j + 2, P_c)))
-                sg = [self.buf(("S", "S1")[i], Rb * ny * Cp) for i in range(len(js))]
-                if two and len(js) == 2 and meet == "y2t":
-                    # both terms in ONE y-stage pass: one output spectrum per block, one input of the inverse; with the shared cross
-                    # block three products per mode (geobo_toeplitz_y2s), otherwise four (geobo_toeplitz_y2t)
-                    if y2s_tabs is not None and y2s_tabs[0] == j:
-                        y2s_fn = hip.spectral_y2s if self.y_mfma else hip.toeplitz_y2s
-                        fn = lambda: y2s_fn(ny, C, Rb, t2g, t2m, y2s_tabs[1], y2s_tabs[2], y2s_tabs[3], sg, plane=Cp)
-                        kname, nprod = "kernel:toeplitz_y2s", 3
-                    else:
-                        fn = lambda: hip.toeplitz_y2t(ny, C, Rb, t2g, t2m, [gens_g[jj] for jj in js], [gens_m[jj] for jj in js], sg, plane=Cp)
-                        kname, nprod = "kernel:toeplitz_y2t", 4
-                    self._launch(kname, 8.0 * Rb * C * (2 * ny + 2 * ny), Rb, self.y_stage_flop(2, 2, shared=nprod == 3), fn)
-                    for i, jj in enumerate(js):
-                        hip.xz2d_fold_inv_ss(nx, Rb, ny, sg[i], ny * Cp, Cp, self.F["x"], self.F["z"], ss[jj])
-                    continue
-                self._ystage(ny, C, Rb, t2g, [gens_g[jj] for jj in js], sg, 0, ny, Cp)
-                sm = None
-                if two and meet == "add":
-                    self._ystage(ny, C, Rb, t2m, [gens_m[jj] for jj in js], sg, 0, ny, Cp, accumulate=True)     # the terms meet in the spectrum
-                elif two:
-                    sm = [self.buf(("Sb", "S1b")[i], Rb * ny * Cp) for i in range(len(js))]
-                    self._ystage(ny, C, Rb, t2m, [gens_m[jj] for jj in js], sm, 0, ny, Cp)
-                for i, jj in enumerate(js):
-                    hip.xz2d_fold_inv_ss(nx, Rb, ny, sg[i], ny * Cp, Cp, self.F["x"], self.F["z"], ss[jj],
-                                         src2=sm[i] if sm is not None else None, in2_row=ny * Cp, r2_first=0)
+            for jj in range(P_c):
+                hip.sumsq_accum(vg[jj], vm[jj] if vm else None, Rb, ss[jj].view(ss[jj].shape[0], -1))
 
     def has_two_term_product(self, nblocks):
         """Whether the y stage of this grid joins the two terms of a row for `nblocks` property blocks (product_two_term): the
@@ -691,30 +701,8 @@ class SpectralProduct:
         """outs[j][r, :] = Zg[r] * K_0j + Zm[r] * K_1j for r < rows <= R: the storing counterpart of reduce_ss's two-term rows.  The
         terms meet in the y stage (one pass for a pair of blocks -- with y2s tables three products per mode --, or the second term
         accumulating into the first one's spectrum), ONE storing inverse transform per block.  Grids: has_two_term_product."""
-        ny, C, Cp = self.ny, self.Px * self.Pz, self.Cp
-        P_c, meet = len(gens_g), self.forms.y_two_term
-        assert self.has_two_term_product(P_c) and rows <= self.R
-        t2g = self.forward_zx(Zg, rows, self.G, src_row_stride=Zg.stride(0), out_name="T2")
-        t2m = self.forward_zx(Zm, rows, self.G, src_row_stride=Zm.stride(0), out_name="T2b")
-        for j in range(0, P_c, 2 if meet == "y2t" else 3):
-            js = list(range(j, min(j + (2 if meet == "y2t" else 3), P_c)))
-            u2 = [self.buf(("S", "S1", "S2")[i], rows * ny * Cp) for i in range(len(js))]
-            gg, gm = [gens_g[jj] for jj in js], [gens_m[jj] for jj in js]
-            if meet == "y2t" and y2s is not None and y2s[0] == j:
-                y2s_fn = hip.spectral_y2s if self.y_mfma else hip.toeplitz_y2s
-                fn = lambda: y2s_fn(ny, C, rows, t2g, t2m, y2s[1], y2s[2], y2s[3], u2, plane=Cp)
-                self._launch("kernel:toeplitz_y2s", 8.0 * rows * C * 4 * ny, rows, self.y_stage_flop(2, 2, shared=True), fn)
-            elif meet == "y2t":
-                fn = lambda: hip.toeplitz_y2t(ny, C, rows, t2g, t2m, gg, gm, u2, plane=Cp)
-                self._launch("kernel:toeplitz_y2t", 8.0 * rows * C * 4 * ny, rows, self.y_stage_flop(2, 2), fn)
-            elif self.forms.y3t:
-                fn = lambda: hip.spectral_y3t(ny, C, rows, t2g, t2m, gg, gm, u2, plane=Cp)
-                self._launch("kernel:toeplitz_y", 8.0 * rows * C * ny * (2 + len(js)), rows, self.y_stage_flop(2, len(js)), fn)
-            else:
-                self._ystage(ny, C, rows, t2g, gg, u2, 0, ny, Cp)
-                self._ystage(ny, C, rows, t2m, gm, u2, 0, ny, Cp, accumulate=True)
-            for i, jj in enumerate(js):
-                self.backward_xz(u2[i], rows, 0, ny, [(0, ny, outs[jj], outs[jj].stride(0))])
+        assert self.has_two_term_product(len(gens_g)) and rows <= self.R
+        self._drive([(0, rows, 2)], [(Zg, 0, gens_g), (Zm, 0, gens_m)], self._store([(0, self.ny, outs)], 0, self.ny), 0, self.ny, y2s=y2s)
 
     def flops_ss(self, rows_one, rows_two, nblocks, shared=False):
         """Executed flop of reduce_ss: rows_one one-term rows, rows_two two-term rows (forward transform per term, y stage, one second

@@ -158,23 +158,12 @@ class TransposedPosteriorMixin:
             self._timed("posterior_zgemm", fl, zgemm, alg=alg)
             vec_of = lambda func, wv, out: hip.colgemv((Ag if func == "grav" else Am)[:Msp, :N], wv, out=out[0], ws=cws)
         mu_l = self._timed("posterior_mean", 0.0, lambda: self._mean_rows(step, w, vec_of)).reshape(-1)
-        slots = hip.xz2d_fold_inv_ss_slots(nx, sp.R, ny)
-        ss = [self._workspace("post_ss_%d" % jj, (slots, ny, nx * nz)) for jj in range(P_c)]
-        for t in ss:
-            t.zero_()
-        gens_g, gens_m = [step.gens[(0, j)] for j in props], [step.gens[(1, j)] for j in props]
         zx = lat and zx
-        swap = (lambda g: g.view(ny, sp.Px, sp.Pz).transpose(1, 2).contiguous().view(-1)) if zx else (lambda g: g)   # tables of transposed planes
-        tg, tm = [swap(g) for g in gens_g], [swap(g) for g in gens_m]
-        # blocks (0, 1) and (1, 0) of a symmetric prior coincide: three y-stage products per two-term row instead of four
-        y2s = sp.y2s_tables(tg, tm) if tuple(props[:2]) == (0, 1) else None
+        ss, tg, tm, y2s, voxel_order = self._ss_cubes(step, zx)
         shared = y2s is not None and P_c == 2
         self._timed("posterior_spectral", sp.flops_ss(Msp, Msp, P_c, shared), lambda: sp.reduce_ss(Zg, 2 * Msp, tg, Zm, Msp, tm, ss, y2s=y2s),
                     valu=sp.valu_ss(Msp, Msp, P_c, shared))
-        if zx:
-            ssum = torch.stack([t.sum(0).view(ny, nz, nx).transpose(1, 2).reshape(-1) for t in ss])   # planes came out as [iz][ix]
-        else:
-            ssum = torch.stack([t.sum(0).reshape(-1) for t in ss])                        # (P_c, N), voxel order (iy, ix, iz)
+        ssum = torch.stack([voxel_order(t) for t in ss])                                  # (P_c, N)
         if Md:
             # K_2j[drill voxels, :]: the drill rows of A K, already there (fp64, every voxel column: _zpath_ok), zero rows behind them
             Kd = [AK[2 * Msp:, jj * self.nc:(jj + 1) * self.nc] for jj in range(P_c)] if self.nc >= N and self.c0 == 0 else None
@@ -182,6 +171,23 @@ class TransposedPosteriorMixin:
                 step, Linv, 0, Md, (lambda Lv, n, func, out: self._lattice_Z(Lv, n, func, A_g if func == "grav" else A_m, out)) if lat else None, Ag, Am,
                 Kd=Kd, y2s=None if zx else y2s))             # (zx: y2s holds the tables of the transposed planes)
         return mu_l, (amp * 1.0 - ssum).reshape(-1)
+
+    def _ss_cubes(self, step, zx):
+        """What both transposed posteriors hand to sp.reduce_ss, and the way back: (ss, tg, tm, y2s, voxel_order).  ss: the zeroed partial
+        cubes post_ss_* (sp.ss_slots() slots per block); tg / tm: the step's generators of the blocks (0, j) / (1, j), as tables of
+        transposed planes where the rows of Z come as [iy][iz][ix] (zx); y2s: their three-product tables -- blocks (0, 1) and (1, 0) of
+        a symmetric prior coincide: three y-stage products per two-term row instead of four.  voxel_order(t): one block's cube summed
+        over its slots, N values in voxel order (iy, ix, iz)."""
+        props, sp, nx, ny, nz = step.props, self._spectral, self.nx, self.ny, self.nz
+        ss = [self._workspace("post_ss_%d" % jj, (sp.ss_slots(), ny, nx * nz)) for jj in range(len(props))]
+        for t in ss:
+            t.zero_()
+        swap = (lambda g: g.view(ny, sp.Px, sp.Pz).transpose(1, 2).contiguous().view(-1)) if zx else (lambda g: g)
+        tg, tm = [swap(step.gens[(0, j)]) for j in props], [swap(step.gens[(1, j)]) for j in props]
+        y2s = sp.y2s_tables(tg, tm) if tuple(props[:2]) == (0, 1) else None
+        if zx:                                                                            # planes came out as [iz][ix]
+            return ss, tg, tm, y2s, lambda t: t.sum(0).view(ny, nz, nx).transpose(1, 2).reshape(-1)
+        return ss, tg, tm, y2s, lambda t: t.sum(0).reshape(-1)
 
     def _mean_rows(self, step, w, vec_of):
         """Posterior mean (P_c, N):  mu_j = (A3 K)[:, block j]^T w  re-associated as  K_.j (A3^T w)  -- the covariance blocks are

@@ -816,6 +816,8 @@ def test_full_size_64cube_properties():
     import bench
     from geobo_amd.config_loader import Settings
     from geobo_amd.inversion import Inversion
+    gc.collect()                         # (two 64^3 engines live side by side below: no room for an earlier test's engine <-> closure cycles)
+    torch.cuda.empty_cache()
     n = 64
     s = Settings(dict(xmax=100.0 * n, ymax=100.0 * n, zLcube=100.0 * n, xNcube=n, yNcube=n, zNcube=n, kernelfunc="matern32"))
     inv = Inversion(settings=s, props=(0, 1), operators="resident")   # method="auto" -> spectral route at 64^3; the operator tensors are read below
