@@ -113,6 +113,8 @@ SIGNATURES = {
     "geobo_trace_stats_ws_bytes": (_sz, [_i64, _i64, _int]),
     "geobo_trace_stats": (_int, [_i64, _dp, _i64, _i64, _int, _int, _int, _int, _int, C.POINTER(_f64), C.POINTER(_f64), _dp, _i64, _dp, _dp, _int,
                                  _int, _int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
+    "geobo_factor_append": (_int, [_int, _dp, _i64, _dp, _i64, _dp, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _dp]),
+    "geobo_rows_downdate": (_int, [_dp, _i64, _i64, _i64, _dp, _dp, _dp, _dp]),
     "geobo_trmv_stats": (_int, [_i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _dp]),
     "geobo_mfma_f64_peak": (_int, [_int, _int, _dp, _dp]),
     "geobo_mfma_mix": (_int, [_int, _int, _int, _int, _dp, _dp]),

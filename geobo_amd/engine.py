@@ -50,6 +50,7 @@ from .pointpred import PointPredictionMixin
 from .resources import ResourceMixin
 from .geobodies import GeobodyMixin
 from .intercepts import InterceptMixin
+from .append import AppendRowsMixin
 from .step import Prior, Step
 from .sharding import (EmulatedGroup, allreduce_sum_, assemble_columns, backend_of, exchange_blocks, exchange_blocks_finish,
                        exchange_blocks_start, gather_rows, gather_slices, shard_columns)
@@ -146,7 +147,7 @@ def _on_device(fn):
 
 
 class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixin, SetStatisticsMixin, CrossValidationMixin, BlockSupportMixin,
-                      PointPredictionMixin, ResourceMixin, GeobodyMixin, InterceptMixin):
+                      PointPredictionMixin, ResourceMixin, GeobodyMixin, InterceptMixin, AppendRowsMixin):
     def __init__(self, settings, device=None, rank=0, world=1, group=None, profile=False, method="auto", assembly="f64",
                  operators="resident"):
         """assembly "f32": covariance tables rounded through fp32 and A K kept in fp32 in HBM (BASELINE config 5, "fp32 kernel
@@ -1004,10 +1005,12 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                 out["logl"] = -0.5 * (st[0] + st[1] + self.N * math.log(2 * math.pi))  # inversion.py:107-110
             else:
                 out["logl"] = 0.0
+        mv = None       # (device mean, device variance, elements between their property blocks): what append_drill_rows starts from
         if not want_mean_var:
             check_factor()
         if want_mean_var and step.rowpath:
             mu_f, var_f = self._posterior_rows(step, Linv, u)
+            mv = (mu_f, var_f, self.N)
             N_ = len(props) * self.N
             hq = self._to_host_async(torch.cat([mu_f.reshape(-1)[:N_], var_f.reshape(-1)[:N_]]), 0)
             check_factor()
@@ -1041,6 +1044,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                     return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
                 mu_l, var_l = self._timed("posterior_reduce", fl, panels, alg=(1.0 * Mu * Mu + 4.0 * Mu) * nv)
             one = self.world == 1 and self.N == self.N_pad
+            mv = (mu_l, var_l, self.nc) if self.world == 1 else None
             N_ = len(props) * self.N
             hq = self._to_host_async(torch.cat([mu_l.reshape(-1)[:N_], var_l.reshape(-1)[:N_]]), 0) if one else None
             check_factor()
@@ -1058,7 +1062,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         # unwritten: that buffer goes under AK_partial (the tests' oracle contacts read its assembled blocks); the row form has none
         whole = AK is not None and not step.sym
         self.last = _LastStep(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props,
-                              sel=sel, ops=(A_g, A_m), step=step)
+                              sel=sel, ops=(A_g, A_m), step=step, mv=mv, uu=out.get("uu"), logdet=out.get("logdet"))
         if step.mirror and step.mirror < self.Ms:
             # a mirrored step left the magnetic rows behind step.mirror unwritten.  Nothing of the engine reads them (AkA was their only
             # reader); whoever asks for the buffer gets them by the mirrored row copy, once, so that no stale row is ever seen

@@ -933,6 +933,37 @@ def set_logdet(G, Kpp, sigma2, idx, n_obs, observed=None, out=None, status=None)
     return out, status
 
 
+def factor_append(D, G, r, Ls, T, uP, out=None, status=None):
+    """S = D - G (k x k, k <= 128, lower triangles read), S = Ls Ls^T, T = Ls^-1, uP = T r (geobo_factor_append, one workgroup).
+    D, G, Ls, T: 2-D fp64 views with unit column stride (k rows and columns used); r, uP: k doubles.  Returns (out (1,) = sum log
+    diag Ls, status (1,) int32 = 0, or 1 + the failing pivot -- then nothing else was written)."""
+    lib = require_gpu()
+    k = _chk(r, "r").numel()
+    lds = [_rowmajor(t, nm) for t, nm in ((D, "D"), (G, "G"), (Ls, "Ls"), (T, "T"))]
+    assert all(t.shape[0] >= k and t.shape[1] >= k for t in (D, G, Ls, T)) and r.is_contiguous()
+    assert _chk(uP, "uP").numel() >= k and uP.is_contiguous()
+    if out is None:
+        out = torch.empty(1, dtype=F64, device=D.device)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=D.device)
+    _lib.check(lib.geobo_factor_append(int(k), _p(D), lds[0], _p(G), lds[1], _p(r), _p(Ls), lds[2], _p(T), lds[3], _p(uP),
+                                       _p(_chk(out, "out")), _p(status), _stream()), "geobo_factor_append")
+    return out, status
+
+
+def rows_downdate(V, n, c, mu, var, ncols=None):
+    """mu[j] += sum_{r < n} c[r] V[r, j], var[j] -= sum_{r < n} V[r, j]^2 for j < ncols (geobo_rows_downdate): rows in ascending
+    order from the stored values, so a split of the rows over several calls gives the same bits."""
+    lib = require_gpu()
+    ld = _rowmajor(V, "V")
+    n = int(n)
+    ncols = V.shape[1] if ncols is None else int(ncols)
+    assert 0 <= n <= V.shape[0] and ncols <= V.shape[1] and _chk(c, "c").numel() >= n and c.is_contiguous()
+    assert _chk(mu, "mu").numel() >= ncols and _chk(var, "var").numel() >= ncols and mu.is_contiguous() and var.is_contiguous()
+    _lib.check(lib.geobo_rows_downdate(_p(V), ld, n, ncols, _p(c), _p(mu), _p(var), _stream()), "geobo_rows_downdate")
+    return mu, var
+
+
 def kinv_diag_ws_doubles(m):
     return max(_lib.load().geobo_kinv_diag_ws_bytes(int(m)) // 8, 1)
 

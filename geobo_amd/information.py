@@ -38,6 +38,23 @@ def _vertical_bases(idx, nz):
     return base
 
 
+def _tile_range(rows, Mv):
+    """The row range of a tile sweep: all Mv valid rows, or the caller's (r0, r1) within them."""
+    if rows is None:
+        return 0, Mv
+    r0, r1 = int(rows[0]), int(rows[1])
+    if not 0 <= r0 <= r1 <= Mv:
+        raise ValueError("rows must lie within the %d valid rows, got %r" % (Mv, rows))
+    return r0, r1
+
+
+def _tile_rows(V, n, skip):
+    """(Vs, n) of a tile whose first `skip` rows lie in front of the row range (tiles start at multiples of the tile height)."""
+    if skip <= 0:
+        return V, n
+    return [v[skip:] for v in V], n - skip
+
+
 class SetStatisticsMixin:
     def _set_sampler(self, prior):
         """PriorSampler whose exact circulant product applies K (generic source), cached per hyper-parameters."""
@@ -52,11 +69,11 @@ class SetStatisticsMixin:
             hit = self._set_smp = (key, smp)
         return hit[1]
 
-    def _v_spectral(self, step, prior, Linv, A_g, A_m, blocks=(2,)):
+    def _v_spectral(self, step, prior, Linv, A_g, A_m, blocks=(2,), rows=None):
         """Tiles (Vs, n) of 128 rows of V_a for every property block a of `blocks` in lockstep (Vs: one tile per block) on the
         transposed route, voxel order (iy, ix, iz): the generators of the step whose factor Linv is where it kept them, the others
         from `prior`.  The rows of Z are formed once per tile and every operator term is ONE product for all the blocks (Z is
-        transformed once)."""
+        transformed once).  rows = (r0, r1): the rows r0 .. r1 only (_tile_range)."""
         sel_t, Md = step.sel_t, step.Md
         sp, N, Msp, T = self._spectral, self.N, self.Ms_pad, 128
         lat = (self._gram is not None and self._gram.edge_supported() and Msp == self.nx * self.ny and self.route.opt("z_lattice")
@@ -70,9 +87,9 @@ class SetStatisticsMixin:
         # (the drill block keeps the buffers it had before the other blocks came)
         V = [self._workspace2d("set_V" if a == 2 else "set_V%d" % a, T, N) for a in blocks]
         tmp = [self._workspace2d("set_Vt" if a == 2 else "set_Vt%d" % a, T, N) for a in blocks]
-        Mv = 2 * Msp + Md
-        for b0 in range(0, Mv, T):
-            n = min(T, Mv - b0)
+        r0, r1 = _tile_range(rows, 2 * Msp + Md)
+        for b0 in range(r0 // T * T, r1, T):
+            n = min(T, r1 - b0)
             terms = []
             for func, A, Ar, c0, Z, g in (("grav", A_g, None if lat else Ag, 0, Zg, gens[0]), ("magn", A_m, None if lat else Am, Msp, Zm, gens[1])):
                 if b0 + n <= c0:
@@ -91,40 +108,41 @@ class SetStatisticsMixin:
                 sp.product(Z, n, g, tmp)
                 for v, t in zip(V, tmp):
                     v[:n].add_(t[:n])
-            yield V, n
+            yield _tile_rows(V, n, r0 - b0)
 
-    def _v_generic(self, step, prior, Linv, A_g, A_m, AK, blocks=(2,)):
+    def _v_generic(self, step, prior, Linv, A_g, A_m, AK, blocks=(2,), rows=None):
         """Tiles (Vs, n) of 256 rows of V_a for every property block a of `blocks` on any one-rank fp64 step, voxel order
-        (iy, ix, iz).  Vs[i] holds N columns or more."""
+        (iy, ix, iz).  Vs[i] holds N columns or more.  rows = (r0, r1): the rows r0 .. r1 only (_tile_range)."""
         sel_t, Md = step.sel_t, step.Md
         N, Np, Msp, T = self.N, self.N_pad, self.Ms_pad, 256
-        Mv = 2 * Msp + Md
+        r0, r1 = _tile_range(rows, 2 * Msp + Md)
+        start = r0 // T * T
         if AK is not None:
             AKa = [AK[:, a * self.nc:a * self.nc + Np] for a in blocks]
             V = [self._workspace2d("set_V" if a == 2 else "set_V%d" % a, T, Np) for a in blocks]
-            for b0 in range(0, Mv, T):
+            for b0 in range(start, r1, T):
                 e = b0 + T                                  # (M_pad is a multiple of 256: whole tiles; columns >= e of L^-1 are zero)
                 for AKd, v in zip(AKa, V):
                     hip.gemm_nn(Linv[b0:e, :e], AKd[:e], v)
-                yield V, min(T, Mv - b0)
+                yield _tile_rows(V, min(T, r1 - b0), r0 - b0)
             return
         smp = self._set_sampler(prior)
         Zt = torch.empty((T, 3, N), dtype=F64, device=self.device)
         Zp = self._workspace2d("set_Zp", T, Np)
-        for b0 in range(0, Mv, T):
-            n = min(T, Mv - b0)
-            for j, A, r0 in ((0, A_g, 0), (1, A_m, Msp)):
-                if b0 + n <= r0:
+        for b0 in range(start, r1, T):
+            n = min(T, r1 - b0)
+            for j, A, a0 in ((0, A_g, 0), (1, A_m, Msp)):
+                if b0 + n <= a0:
                     Zt[:, j, :].zero_()
                     continue
-                for c0, rows in self._operator_rows(A):
-                    hip.gemm_nn(Linv[b0:b0 + T, r0 + c0:r0 + c0 + rows.shape[0]], rows, Zp, beta=1.0 if c0 else 0.0)
+                for c0, arows in self._operator_rows(A):
+                    hip.gemm_nn(Linv[b0:b0 + T, a0 + c0:a0 + c0 + arows.shape[0]], arows, Zp, beta=1.0 if c0 else 0.0)
                 Zt[:, j, :] = Zp[:, :N]
             Zt[:, 2, :].zero_()
             if Md and b0 + n > 2 * Msp:
                 Zt[:, 2, :][:, sel_t] = Linv[b0:b0 + T, 2 * Msp:2 * Msp + Md]
             KZ = smp.apply_K(Zt[:n])                        # (all three properties come out of the one circulant product)
-            yield [KZ[:, a, :] for a in blocks], n
+            yield _tile_rows([KZ[:, a, :] for a in blocks], n, r0 - b0)
 
     def _zsource(self, step, AK, source):
         """The tile source of a sweep, "spectral" or "generic" ("auto": by the step's route); sets set_source."""
@@ -138,14 +156,15 @@ class SetStatisticsMixin:
         self.set_source = source
         return source
 
-    def _v_tiles(self, source, prior, AK, blocks=(2,)):
-        """Generator of the V tiles of the last step's factor from `source` ("spectral" or "generic")."""
+    def _v_tiles(self, source, prior, AK, blocks=(2,), rows=None):
+        """Generator of the V tiles of the last step's factor from `source` ("spectral" or "generic"); rows = (r0, r1): the rows
+        r0 .. r1 of V only (default: all of them)."""
         last = self.last
         Linv, step = last["Linv"], last["step"]
         A_g, A_m = last["ops"]
         if source == "spectral":
-            return self._v_spectral(step, prior, Linv, A_g, A_m, blocks)
-        return self._v_generic(step, prior, Linv, A_g, A_m, AK if last["AK_complete"] else None, blocks)
+            return self._v_spectral(step, prior, Linv, A_g, A_m, blocks, rows)
+        return self._v_generic(step, prior, Linv, A_g, A_m, AK if last["AK_complete"] else None, blocks, rows)
 
     def set_statistics(self, sets, kernelfunc, lengths, crossweights, gp_amp, gp_sigma, observed=None, source="auto"):
         """Posterior statistics of the drill property over C voxel sets, from the factor of the last posterior() step:
@@ -175,6 +194,11 @@ class SetStatisticsMixin:
                                         float(gp_sigma[2]) ** 2, observed, source, AK)
 
     def _set_statistics(self, sets, prior, sigma2, observed, source, AK):
+        return self._set_logdet(self._set_grams(sets, prior, sigma2, source, AK), observed)
+
+    def _set_grams(self, sets, prior, sigma2, source, AK):
+        """The sweep of _set_statistics on its own: dict(idx, G, Kpp, sigma2) with the Grams G[c] of every set over all rows of V_d and
+        the prior blocks.  A caller that adds rows to the factor keeps it resident and adds the new rows' part (add_rows)."""
         C_, k = sets.shape
         dev = self.device
         idx = torch.as_tensor(sets.astype(np.int32), device=dev)
@@ -200,8 +224,35 @@ class SetStatisticsMixin:
             for c in range(C_):
                 p = tuple(x[pts[c]] for x in xyz)
                 prior.k_block(self, 2, 2, p, p, Kpp[c])
+        return dict(idx=idx, G=G, Kpp=Kpp, sigma2=sigma2,
+                    add_rows=lambda V, n: hip.set_gram(idx, V, n, G, accumulate=True, ncols=self.N))
+
+    def _set_logdet(self, grams, observed):
+        """(info_gain, path_var, sum_var, status) of _set_statistics from the Grams of _set_grams."""
         obs = None
         if observed is not None:
-            obs = torch.as_tensor(np.asarray(observed, dtype=bool).reshape(-1)[:self.N].astype(np.uint8), device=dev)
-        out, status = self._timed("set_logdet", 0.0, lambda: hip.set_logdet(G, Kpp, sigma2, idx, self.N, observed=obs))
+            obs = torch.as_tensor(np.asarray(observed, dtype=bool).reshape(-1)[:self.N].astype(np.uint8), device=self.device)
+        out, status = self._timed("set_logdet", 0.0, lambda: hip.set_logdet(grams["G"], grams["Kpp"], grams["sigma2"], grams["idx"], self.N,
+                                                                            observed=obs))
         return out[0], out[1], out[2], status
+
+    def set_grams(self, sets, kernelfunc, lengths, crossweights, gp_amp, gp_sigma, source="auto"):
+        """set_statistics in two parts for a caller that appends drill rows in between (append.py): the Grams of `sets` over every row
+        of V_d, kept on the device; grams["add_rows"] is append_drill_rows' tile_hook, set_logdet_from(grams, observed) the statistics.
+        Arguments and conditions of set_statistics."""
+        from .engine import weight_matrix
+        from .step import Prior
+        last, AK = self._append_ready("set_grams()")
+        sets = np.asarray(sets)
+        if sets.ndim != 2 or not 1 <= sets.shape[1] <= SET_K_MAX:
+            raise ValueError("sets must be a (C, k) index table with 1 <= k <= %d" % SET_K_MAX)
+        if np.any(sets >= self.N):
+            raise ValueError("set entries must be flat voxel indices below N = %d (negative: padding)" % self.N)
+        with torch.cuda.device(self.device):
+            return self._set_grams(sets.astype(np.int64), Prior(kernelfunc, lengths, weight_matrix(crossweights), float(gp_amp)),
+                                   float(gp_sigma[2]) ** 2, source, AK)
+
+    def set_logdet_from(self, grams, observed=None):
+        """The statistics of set_statistics from set_grams' resident Grams (observed as there)."""
+        with torch.cuda.device(self.device):
+            return self._set_logdet(grams, observed)

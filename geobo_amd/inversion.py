@@ -362,6 +362,76 @@ class Inversion:
             var = [var_cubes[i] * scale[i] ** 2 for i in range(3)]
         return rec[0], rec[1], rec[2], var[0], var[1], var[2]
 
+    # ---- new drill values without a new step --------------------------------------------------------------
+    def _new_drill_rows(self, voxels, values, normalised=False):
+        """(flat voxel indices, values in the GP's normalised units) of new drill observations, checked on the host: voxels as flat
+        (iy, ix, iz) indices or a (k, 3) array of (iy, ix, iz); values in data units unless `normalised` -- then they are z-scored with
+        the mean and population std of cubing()'s own drillfield (the survey's normalisation is frozen)."""
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("assimilate_drill() adds rows to the survey of cubing(): call cubing() first")
+        s = self.settings
+        ny, nx, nz = s.yNcube, s.xNcube, s.zNcube
+        N = ny * nx * nz
+        vox = np.asarray(voxels)
+        if vox.size and not np.issubdtype(vox.dtype, np.integer):
+            raise ValueError("voxels must be integer indices")
+        if vox.ndim == 2 and vox.shape[1] == 3:
+            if np.any(vox < 0) or np.any(vox >= np.array([ny, nx, nz])):
+                raise ValueError("voxel indices (iy, ix, iz) must lie inside the (%d, %d, %d) cube" % (ny, nx, nz))
+            vox = (vox[:, 0].astype(np.int64) * nx + vox[:, 1]) * nz + vox[:, 2]
+        elif vox.ndim != 1:
+            raise ValueError("voxels must be flat (iy, ix, iz) indices or a (k, 3) index array")
+        vox = vox.astype(np.int64)
+        vals = np.asarray(values, dtype=np.float64).reshape(-1)
+        if vals.size != vox.size:
+            raise ValueError("%d values for %d voxels" % (vals.size, vox.size))
+        if vox.size < 1:
+            raise ValueError("assimilate_drill() needs at least one voxel")
+        if np.any(vox < 0) or np.any(vox >= N):
+            raise ValueError("voxels must be flat voxel indices in [0, %d)" % N)
+        if np.unique(vox).size != vox.size:
+            raise ValueError("voxels repeat: one drill value per voxel")
+        seen = np.intersect1d(vox, self._sel)
+        if seen.size:
+            raise ValueError("voxels %s carry a drill value already" % seen[:8])
+        if not normalised:
+            d = np.asarray(self.drillfield, dtype=np.float64)
+            if not d.size or not d.std() > 0.0:
+                raise ValueError("cubing()'s drillfield has no spread: new values cannot be normalised; pass normalised=True")
+            vals = (vals - d.mean()) / d.std()
+        return vox, vals
+
+    def assimilate_drill(self, voxels, values, normalised=False):
+        """New drill values after cubing(), without a new step: the factor of cubing()'s step is extended by one row per voxel
+        (PosteriorEngine.append_drill_rows) and the six cubes are updated in place of recomputed.  voxels: flat (iy, ix, iz) indices or
+        a (k, 3) index array of voxels that carry no drill value yet; values: in data units (normalised=True: already in the GP's units).
+        The survey's normalisation is FROZEN: new values are z-scored with the mean and population std of cubing()'s drillfield, and
+        the cubes come back in cubing()'s units.  A fresh cubing() on the union of the data re-normalises all three data vectors from
+        the union and therefore returns (slightly) different cubes; this call gives what the reference's GP gives for the union at the
+        survey's own normalisation.  The rows are appended to the survey (a later rebuild of the factor contains them), mu_rec,
+        cov_rec and logl follow, and every product that works from the step's factor sees them.  Returns the six cubes."""
+        vox, vals = self._new_drill_rows(voxels, values, normalised)
+        self._ensure_factor()
+        last = self.engine.last
+        if last.get("uu") is None or not self.engine.mean_var_known():
+            # the factor was rebuilt without the likelihood or the mean (after a refactoring campaign, a cross-validation at other
+            # parameters), or rows went in or out without the mean: one whole step gives the state the rows are appended to
+            self._run(self.gp_amp, self.gp_length, None, True, True)
+        r = self.engine.append_drill_rows(vox, vals, want_mean_var=True)
+        self._sel = np.concatenate([np.asarray(self._sel, dtype=np.int64), vox])
+        self.Fs3 = np.hstack((self.Fs3, vals))
+        self.mu_rec, self.cov_rec = r["mu"], DiagonalCovariance(r["var"])
+        if "uu" in r:
+            self.logl = r["logl"]
+        s = self.settings
+        shape = (3, s.yNcube, s.xNcube, s.zNcube)
+        mean_cubes, var_cubes = self.mu_rec.reshape(shape), r["var"].reshape(shape)
+        scale = self._cube_scale
+        with np.errstate(all="ignore"):
+            rec = [mean_cubes[i] * scale[i] for i in range(3)]
+            var = [var_cubes[i] * scale[i] ** 2 for i in range(3)]
+        return rec[0], rec[1], rec[2], var[0], var[1], var[2]
+
     # ---- posterior realisations (DESIGN.md section 12) ---------------------------------------------------------------------------
     def _prior_sampler(self, approximate):
         """PriorSampler of the current hyper-parameters (cached per grid, kernel, lengths, weights, amplitude)."""
@@ -1009,14 +1079,18 @@ class Inversion:
         cols.update({"STD_" + n: out["std"][i] for i, n in enumerate(names)})
         pd.DataFrame(cols).to_csv(os.path.join(self.settings.outpath, fname), index=False)
 
-    def propose_drill_campaign(self, q, utility="information", costs=None, write=False):
+    def propose_drill_campaign(self, q, utility="information", costs=None, write=False, update="refactor"):
         """A greedy batch of q distinct vertical holes ("kriging believer"): pick the best inner hole by `utility` ("information",
         "ucb", "ucb_path"; see geobo_amd.campaign), add its voxels that carry no drill row yet as drill rows whose values are the
         posterior mean (which leaves the mean unchanged), refactor without the mean and variance, score again without the chosen holes.
         The statistics leave out voxels that already carry a drill row (they would not be measured again); the mean and cost sums run
         over the whole hole, as the reference's.  Returns a DataFrame (NORTHING, EASTING at voxel centres, RANK, UTILITY, INFO_GAIN,
         PATH_STD) and sets `campaign_info` (chosen voxel sets, the three variance cubes after all q holes in cubing()'s units, and the
-        mean cubes of that step).  The Inversion is left as cubing() left it; the engine's factor is rebuilt from the real data."""
+        mean cubes of that step).  The Inversion is left as cubing() left it; the engine's factor is rebuilt from the real data.
+        update="append": the same campaign without a step per pick -- the hole Grams of one sweep stay on the device, every pick's rows
+        are appended to the factor at the posterior mean (PosteriorEngine.append_drill_rows; u_P = 0, the mean keeps its bits) and
+        only their rows of V_d are added to the Grams; at the end the rows are dropped again (truncate_drill_rows) in place of the
+        restoring step.  DESIGN.md section 20."""
         import os
 
         import pandas as pd
@@ -1024,6 +1098,8 @@ class Inversion:
         self._cubing_done("propose_drill_campaign()")
         if utility not in campaign.UTILITIES:
             raise ValueError("utility must be one of %s, got %r" % (campaign.UTILITIES, utility))
+        if update not in ("refactor", "append"):
+            raise ValueError("update must be 'refactor' or 'append', got %r" % (update,))
         s = self.settings
         ny, nx, nz = s.yNcube, s.xNcube, s.zNcube
         N = nx * ny * nz
@@ -1051,14 +1127,25 @@ class Inversion:
             return eng.posterior(A_g, A_m, sel, y_g, y_m, values[sel], lengths, self.coeffm, s.kernelfunc, self.gp_sigma, gp_amp=self.gp_amp,
                                  props=(0, 1, 2), calclogl=False, want_mean_var=want_mean_var)
         picks, rows = [], []
+        append = update == "append"
+        if append:
+            self._ensure_factor()
+            if not eng.mean_var_known():
+                self._run(self.gp_amp, self.gp_length, None, False, True)      # (a factor rebuilt without the mean: the appends carry it)
+            params, Md0 = self._step_params, eng.last["step"].Md
+            grams = eng.set_grams(sets, s.kernelfunc, lengths, self.coeffm, self.gp_amp, self.gp_sigma)
+            r = dict(mu=np.asarray(self.mu_rec), var=np.asarray(np.diag(self.cov_rec)))
         try:
             self._step_params = None            # from here on the factor holds fantasised rows
             for rank in range(q):
-                step(sel, False)
                 observed = np.zeros(N, dtype=bool)
                 observed[sel] = True
-                ig, pv, sv, st = (t.cpu().numpy() for t in eng.set_statistics(sets, s.kernelfunc, lengths, self.coeffm, self.gp_amp,
-                                                                                 self.gp_sigma, observed=observed))
+                if append:
+                    ig, pv, sv, st = (t.cpu().numpy() for t in eng.set_logdet_from(grams, observed=observed))
+                else:
+                    step(sel, False)
+                    ig, pv, sv, st = (t.cpu().numpy() for t in eng.set_statistics(sets, s.kernelfunc, lengths, self.coeffm, self.gp_amp,
+                                                                                     self.gp_sigma, observed=observed))
                 u = campaign.utility(utility, mean_sum, cost_sum, s.kappa, s.beta, info_gain=ig, path_var=pv * ds ** 2, sum_var=sv * ds ** 2)
                 u = np.where(np.isfinite(u), u, -np.inf)
                 u[picks] = -np.inf
@@ -1070,7 +1157,10 @@ class Inversion:
                 new = sets[c][~observed[sets[c]]]
                 values[new] = mu_d[new]
                 sel = np.union1d(sel, new)
-            r = step(sel, True)
+                if append and new.size:
+                    r = eng.append_drill_rows(new, None, want_mean_var=True, tile_hook=grams["add_rows"])
+            if not append:
+                r = step(sel, True)
             shape = (3, ny, nx, nz)
             with np.errstate(all="ignore"):
                 var = [r["var"].reshape(shape)[i] * scale[i] ** 2 for i in range(3)]
@@ -1079,7 +1169,11 @@ class Inversion:
                                       utility=utility)
         finally:
             # the engine's factor back to the real survey (sample_posterior must never condition on fantasised rows)
-            self._run(self.gp_amp, self.gp_length, None, False, False)
+            if append:
+                eng.truncate_drill_rows(Md0)
+                self._step_params = params
+            else:
+                self._run(self.gp_amp, self.gp_length, None, False, False)
         table = pd.DataFrame(rows, columns=["I0", "I1", "RANK", "UTILITY", "INFO_GAIN", "PATH_STD"])
         table.insert(0, "NORTHING", table.pop("I0") * s.yvoxsize + s.ymin + 0.5 * s.yvoxsize)
         table.insert(1, "EASTING", table.pop("I1") * s.xvoxsize + s.xmin + 0.5 * s.xvoxsize)

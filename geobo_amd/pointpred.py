@@ -56,6 +56,34 @@ class PointPredictionMixin:
             return self._predict_points((qx, qy, qz), Prior(kernelfunc, lengths, weight_matrix(crossweights), float(gp_amp)), bool(full_cov),
                                         hip.pad_n(batch), int(limit_bytes), None if op_rows is None else int(op_rows))
 
+    def _points_op_batch(self, op_rows=None):
+        """(rows per batch of a streamed operator, workspace slot of the batch) for _points_columns; None: what a STREAM_ROWS_BYTES
+        buffer holds in whole 256-row tiles."""
+        if op_rows is None:
+            op_rows = min(self.Ms_pad, max(256, STREAM_ROWS_BYTES // (8 * self.N_pad) // 256 * 256))
+        return op_rows, "cond_op_rows" if op_rows == 256 else "points_op_rows"
+
+    def _points_columns(self, prior, qb, blocks, Cb, sel_xyz, Md, op_rows, slot, n_valid):
+        """Cb[i] = C*_a = A3 K_{.a}(grid, Q) for a = blocks[i] and the column points qb (a whole number of 128-point units): the
+        sensor rows through geobo_ak_points against the row batches of the last step's operators, the Md drill rows (voxel
+        coordinates sel_xyz) through geobo_k_block, zero behind them.  Cb[i]: (M_pad x len(qb)) views.  n_valid: the points that
+        are no padding (flop accounting only).  predict_points and append_drill_rows (append.py) share it."""
+        Msp = self.Ms_pad
+        off_d = 2 * Msp
+        nb = qb[0].numel()
+        for s_, A in enumerate(self.last["ops"]):
+            # operator rows as condition() reads them: zero padded, so the padding rows of C* come out zero
+            for r0, rows in self._operator_rows(A, op_rows, slot):
+                R = rows.shape[0]
+                for a, C_a in zip(blocks, Cb):
+                    out = C_a[s_ * Msp + r0:s_ * Msp + r0 + R]
+                    self._timed("points_ak", 2.0 * R * self.N_pad * nb, lambda: prior.ak_points(self, s_, a, rows, qb, out),
+                                alg=2.0 * min(R, self.Ms - r0) * self.N * n_valid)
+        for a, C_a in zip(blocks, Cb):
+            C_a[off_d + Md:].zero_()
+            if Md:
+                prior.k_block(self, 2, a, sel_xyz, qb, C_a[off_d:off_d + Md])
+
     def _predict_points(self, q_xyz, prior, full_cov, batch, limit_bytes, op_rows):
         dev, last = self.device, self.last
         Linv, u = last["Linv"], last["u"]
@@ -83,27 +111,15 @@ class PointPredictionMixin:
         ws = self._workspace("points_post_ws", (hip.posterior_ws_doubles(M_pad, batch),))
         # a streamed operator: each row batch is generated once per query batch and serves the three properties.  256 rows x one
         # query batch are a few dozen workgroups per launch, so the batch grows to what a fixed buffer holds (whole 256-row tiles)
-        if op_rows is None:
-            op_rows = min(Msp, max(256, STREAM_ROWS_BYTES // (8 * self.N_pad) // 256 * 256))
-        slot = "cond_op_rows" if op_rows == 256 else "points_op_rows"
+        op_rows, slot = self._points_op_batch(op_rows)
         # executed flop of the reduction: as posterior() counts them (triangular L^-1, 64-row groups)
         tri = sum(64.0 * 64 * g + 2560.0 for g in range((Mv + 63) // 64))
         for b0 in range(0, Qp, batch):
             nb = min(batch, Qp - b0)
             qb = tuple(c[b0:b0 + nb] for c in qp)
             Cb = [C[a][:, :nb] for a in range(3)]
-            for s_, A in enumerate(last["ops"]):
-                # operator rows as condition() reads them: zero padded, so the padding rows of C* come out zero
-                for r0, rows in self._operator_rows(A, op_rows, slot):
-                    R = rows.shape[0]
-                    for a in range(3):
-                        out = Cb[a][s_ * Msp + r0:s_ * Msp + r0 + R]
-                        self._timed("points_ak", 2.0 * R * self.N_pad * nb, lambda: prior.ak_points(self, s_, a, rows, qb, out),
-                                    alg=2.0 * min(R, self.Ms - r0) * self.N * min(nb, max(Q - b0, 0)))
+            self._points_columns(prior, qb, (0, 1, 2), Cb, sel_xyz, Md, op_rows, slot, min(nb, max(Q - b0, 0)))
             for a in range(3):
-                Cb[a][Mv:].zero_()
-                if Md:
-                    prior.k_block(self, 2, a, sel_xyz, qb, Cb[a][off_d:off_d + Md])
                 m_a, v_a = self._timed("points_reduce", 2.0 * nb * tri, lambda: hip.posterior_reduce(
                     Linv, Cb[a], u, prior.W[a][a] * prior.amp, ws, m_valid=Mv))
                 mean[a, b0:b0 + nb], var[a, b0:b0 + nb] = m_a, v_a

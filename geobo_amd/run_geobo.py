@@ -35,10 +35,27 @@ def run(settings, method="auto", bayesopt=True, write=True):
         voxelsize = (s.xvoxsize, s.yvoxsize, s.zvoxsize)
         for c, n in zip(cubes, names):
             dataio.create_vtkcube(c, origin, voxelsize, fname=os.path.join(s.outpath, n + ".vtk"))
+    updated = None
+    more = getattr(s, "assimilate_drill", None)           # optional YAML key assimilate_drill: a further drill csv (in inpath, the format
+    if more:                                              # of FNAME_drilldata) whose values are added WITHOUT a new step; every product
+        import copy                                       # below then works from the extended factor
+        s_more = copy.copy(s)
+        s_more.FNAME_drilldata = str(more)
+        extra = np.asarray(dataio.read_drilldata(s_more, s.drill_features, voxelpos)[0][s.ifeature]).reshape(-1)
+        # (a voxel that carries a value already keeps it: one drill row per voxel)
+        new_vox = np.flatnonzero((extra != 0) & (np.asarray(drilldata0).reshape(-1) == 0))
+        if new_vox.size:
+            updated = inv.assimilate_drill(new_vox, extra[new_vox])
+            if write:
+                for c, n in zip(updated, names):
+                    dataio.create_vtkcube(c, origin, voxelsize, fname=os.path.join(s.outpath, n + "_updated.vtk"))
     cv = getattr(s, "cross_validate", None)               # optional YAML key cross_validate: loo | holes | patches
     if cv:
         cv_result = inv.cross_validate(folds=str(cv), write=write)
     out = dict(zip(names, cubes), inversion=inv, drillcoord=drillcoord, inputs=(gravfield, magfield, drillfield, sensor_locations, drilldata0))
+    if updated is not None:
+        out.update({n + "_updated": c for n, c in zip(names, updated)}, assimilated_voxels=new_vox)
+        cubes = updated                                   # (the proposals below look at the cubes with the new values in)
     if cv:
         out["cross_validation"] = cv_result
     bm = getattr(s, "block_model", None)                  # optional YAML key block_model: [bx, by, bz] voxels per block

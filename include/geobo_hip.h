@@ -822,6 +822,24 @@ int geobo_trace_stats(int64_t S, const double* F, int64_t sstride, int64_t pstri
                       double* acc_sum, uint32_t* hist_len, uint32_t* hist_thick, int32_t* detail, double* dsum, void* ws, size_t ws_bytes,
                       void* stream);
 
+/* ---- new drill rows behind a factorised K_y (append.hip) ---------------------------------------------------
+ * geobo_factor_append: S = D - G (k x k, k <= 128; the LOWER triangles of D and G are read, leading dimensions ldd, ldg), Cholesky
+ * S = Ls Ls^T in LDS, T = Ls^-1 in place, one workgroup:
+ *   Ls, T (k x k, leading dimensions ldl, ldt): lower triangular, the strict upper triangle of the k x k block written as zero;
+ *   uP = T r (k; r: k doubles),   logsum[0] = sum log diag Ls,   status[0] = 0;
+ * or status[0] = 1 + the first pivot that is not positive and finite, and NOTHING else is written.  Checks before any device access
+ * (GEOBO_E_ARG): NULL pointers, k < 1, k > 128, a leading dimension < k. */
+int geobo_factor_append(int k, const double* D, int64_t ldd, const double* G, int64_t ldg, const double* r, double* Ls, int64_t ldl,
+                        double* T, int64_t ldt, double* uP, double* logsum, int* status, void* stream);
+
+/* geobo_rows_downdate: for j < ncols, over the n rows of V (n x ld fp64 row-major, ld >= ncols)
+ *     mu[j] += sum_r c[r] V[r, j],     var[j] -= sum_r V[r, j]^2,
+ * each started from the stored value and taken in ascending r with one fma per row: the rows split over several calls give the same
+ * bits.  A stream of n ncols doubles: a thread owns two adjacent columns and loads 16 bytes where V, mu and var are 16-byte aligned
+ * and ld is even, one column and 8 bytes otherwise (the same arithmetic).  No atomics.  n == 0 or ncols == 0 is a no-op.  Checks before
+ * any device access (GEOBO_E_ARG): NULL mu or var, NULL V or c with n > 0, n < 0, ncols < 0, ld < ncols, ncols > 2^38. */
+int geobo_rows_downdate(const double* V, int64_t ld, int64_t n, int64_t ncols, const double* c, double* mu, double* var, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
