@@ -26,6 +26,7 @@ SIGNATURES = {
     "geobo_lattice_wplanes": (_int, [_i64, _int, _int, _int, _dp, _dp, _dp, _dp]),
     "geobo_xz2d_fold_inv_strided": (_int, [_int, _i64, _int, _dp, _i64, _i64, _dp, _dp, _dp, _i64, _i64, _i64, _dp]),
     "geobo_xz2d_fold_inv_mul": (_int, [_int, _i64, _int, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _i64, _i64, _i64, _dp]),
+    "geobo_xz2d_fold_conv_fwd": (_int, [_int, _i64, _int, _dp, _i64, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _i64, _i64, _dp]),
     "geobo_sumsq_accum": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _int, _dp, _i64, _dp]),
     "geobo_lamdot_z": (_int, [_i64, _int, _int, _int, _dp, _dp, _dp, _dp]),
     "geobo_centro_fill": (_int, [_dp, _i64, _i64, _i64, _dp]),

@@ -814,6 +814,305 @@ __global__ void __launch_bounds__(256, 2) xz_fold_inv_kernel(FoldArgs g) {
   }
 }
 
+// ---- rows of L^-1 A as spectra: the MUL inverse and the forward transform of one plane in one workgroup ------------------------
+// (geobo_xz2d_fold_conv_fwd; dense planes, radix 4.)  Plane p = (row r, channel c): the inverse phase is the MUL mode of
+// xz_fold_inv_kernel -- in[c] * in2[r] staged through registers into the ring, radix 4 along both axes -- and leaves the N x N plane
+// in the D fragments of the four waves: lane (lr, q) of wave w holds X[16 r' + 4 q + rho][4 lr + w] in xe[rho >> 1][rho & 1][r'].
+// Hand-off: instead of being stored, the fragments go to LDS in the layout the forward kernel's fragment reads expect -- chunk r' (16
+// rows, 8 KiB), row q + 4 rho of the chunk (rowperm4), 16-byte slots XOR-swizzled by that row -- over the first 32 KiB of the ring,
+// which has been read to its end by then.  The first and the last row of the plane are not the table's: they are taken from
+// edge[r][k][c][.] (k = 0, 1; nullptr: zeros) by the lanes that own them.  The forward phase is xz_fold_fwd_kernel<N, false> with the
+// whole plane already in place: no DMA, no counted waits, one barrier in front of the chunk loop and one behind it.
+// The pipeline of staged loads restarts with every plane (the ring slot of chunk c is c % RING); the other resident workgroup of
+// the CU covers the restart and the store phase.  LDS: RING x 16 KiB + the two 16 KiB class images (RING = 3: 80 KiB, two
+// workgroups per CU; RING = 4: 96 KiB, one -- 1.09 against 0.89 ms per 256 rows x 64 planes, compile-time A/B).
+// XZF_CF_NT_ST: non-temporal stores of the spectrum.  Unlike the forward kernel's (XZF_NT_ST, which stays as it was), this kernel's stores
+// share the CU with the other workgroup's factor loads, which are L2 hits: 0.79 against 0.89 ms.
+#ifndef XZF_CF_RING
+#define XZF_CF_RING 3
+#endif
+#ifndef XZF_CF_NT_ST
+#define XZF_CF_NT_ST 1
+#endif
+
+template <int N, int RING>
+struct ConvFwdCfg {
+  using KI = InvCfg<N, RING>;
+  using KF = FwdCfg<N, 4>;
+  static constexpr size_t RINGB = (size_t)RING * KI::CHB, LDS = RINGB + 2 * 16384;
+  static_assert(RING >= 3 && RINGB >= (size_t)KF::RT * KF::CHB && KF::RT == 4 && KI::RT == 8, "the plane overlays the ring");
+};
+
+template <int N, int RING>
+__global__ void __launch_bounds__(256, 2) xz_conv_fwd_kernel(FoldArgs g) {
+  using KC = ConvFwdCfg<N, RING>;
+  using KI = typename KC::KI;
+  using KF = typename KC::KF;
+  constexpr int H = N / 2, RTI = KI::RT, RTF = KF::RT, KPF = KF::KP, ND = KI::ND;
+  constexpr int out_rowB = 2 * N * 8;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  char* const ring = reinterpret_cast<char*>(smem);
+  double* const mxi = smem + KC::RINGB / 8;                   // inverse: [rho][j][w] of (cos, sin), slots XOR j
+  double* const mxf = mxi + 2048;                             // forward: [rho][w][j] of (cos, sin), slots XOR w
+  const unsigned ring_lds = (unsigned)(uintptr_t)(lds_ptr_t)ring;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, q = lane >> 4;
+
+  for (int idx = tid; idx < 4 * 16 * 16; idx += 64 * 4) {
+    const int rho = idx >> 8, a = (idx >> 4) & 15, b = idx & 15;
+    {
+      const int j = a, om = b, i = 4 * j + rho;               // (as in xz_fold_inv_kernel)
+      const double c = g.Fx[(((int64_t)(4 * om) * H + (i >> 1)) << 1) + (i & 1)];
+      const double sn = g.Fx[(((int64_t)(4 * om + 1) * H + (i >> 1)) << 1) + (i & 1)];
+      *reinterpret_cast<v2d*>(mxi + ((((rho * 16 + j) * 16) + (om ^ j)) << 1)) = (v2d){c, om ? sn : ((j & 1) ? -c : c)};
+    }
+    {
+      const int om = a, j = b, i = 4 * j + rho;               // (as in xz_fold_fwd_kernel)
+      const double c = g.Fx[(((int64_t)(4 * om) * H + (i >> 1)) << 1) + (i & 1)];
+      const double sn = g.Fx[(((int64_t)(4 * om + 1) * H + (i >> 1)) << 1) + (i & 1)];
+      *reinterpret_cast<v2d*>(mxf + ((((rho * 16 + om) * 16) + (j ^ om)) << 1)) = (v2d){c, om ? sn : ((j & 1) ? -c : c)};
+    }
+  }
+  const unsigned fxoff = lr * 256 + (((lr & 12) | (q ^ (lr & 3))) << 4);
+  const unsigned fx4i = (unsigned)(uintptr_t)(lds_ptr_t)mxi + fxoff, fx4f = (unsigned)(uintptr_t)(lds_ptr_t)mxf + fxoff;
+  double gzc[4], gzs[4];                                      // inverse: (cos | sin) row of frequency t + 4 q at z = 4 lr + w
+  {
+    const int i = 4 * lr + w;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int om = t + 4 * q;
+      const double c = g.Fz[(((int64_t)(4 * om) * H + (i >> 1)) << 1) + (i & 1)];
+      const double sn = g.Fz[(((int64_t)(4 * om + 1) * H + (i >> 1)) << 1) + (i & 1)];
+      gzc[t] = c;
+      gzs[t] = om ? sn : ((lr & 1) ? -c : c);
+    }
+  }
+  double gE[KPF], gO[KPF];                                    // forward: F?_z[b = 16 w + lr][j = 4 t + q]
+#pragma unroll
+  for (int t = 0; t < KPF; ++t) {
+    const v2d f = *reinterpret_cast<const v2d*>(g.Fz + (((int64_t)(16 * w + lr) * H + 4 * t + q) << 1));
+    gE[t] = f.x;
+    gO[t] = f.y;
+  }
+  const unsigned xq0 = ring_lds + lr * KI::ROWB + (unsigned)((q << 8) | (lr << 4));
+  // forward fragment t of chunk c of the plane: raddr0 ^ (t << 6), + c * KF::CHB  (slot (4 t + q) ^ lr of row lr)
+  const unsigned raddr0 = ring_lds + lr * KF::ROWB + ((q ^ lr) << 4);
+  // hand-off: element (row 16 r' + 4 q + rho, column 4 lr + w) -> chunk r', row q + 4 rho, slot (2 lr + (w >> 1)) ^ (q + 4 rho):
+  // (hoff0 ^ (rho << 6)) + rho * 4 * ROWB + r' * CHB
+  const unsigned hoff0 = (unsigned)(q * KF::ROWB + ((((2 * lr + (w >> 1)) ^ q)) << 4) + (w & 1) * 8);
+
+  const int64_t first = blockIdx.x, pstep = gridDim.x;
+  if (first >= g.nplanes) return;
+  using rsrc_t = __amdgpu_buffer_rsrc_t;
+  v2d fa[2][ND], fb[2][ND];
+  unsigned fo[ND];
+#pragma unroll
+  for (int j = 0; j < ND; ++j) {
+    const int row = w + 4 * j;
+    fo[j] = (unsigned)((8 * (row & 3) + (row >> 2)) * KI::ROWB + ((lane ^ (row & 15)) << 4));
+  }
+  auto fetch = [&](rsrc_t ra, rsrc_t rb, int c) {
+    const int cb = (32 * (c >> 1) + 4 * (c & 1)) * KI::ROWB;
+#pragma unroll
+    for (int j = 0; j < ND; ++j) {
+      fa[c & 1][j] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(ra, fo[j], cb, 0));
+      fb[c & 1][j] = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(rb, fo[j], cb, 0));
+    }
+  };
+  auto commit = [&](int c, int slot) {
+#pragma unroll
+    for (int j = 0; j < ND; ++j) asm volatile("" : "+v"(fa[c & 1][j]), "+v"(fb[c & 1][j]));
+#pragma unroll
+    for (int j = 0; j < ND; ++j) {
+      const int row = w + 4 * j;
+      *reinterpret_cast<v2d*>(ring + slot * KI::CHB + row * 1024 + (lane << 4)) = fa[c & 1][j] * fb[c & 1][j];
+    }
+  };
+  const unsigned soff = (unsigned)(8 * q * out_rowB + 2 * (16 * w + lr) * 8);
+  __syncthreads();                                            // class images visible
+  for (int64_t p = first; p < g.nplanes; p += pstep) {
+    const int64_t r = p / g.ppr;
+    const int ch = (int)(p % g.ppr);
+    const rsrc_t curA = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g.in + ch * g.in_plane), 0, RTI * KI::CHB, 0x00020000);
+    const rsrc_t curB = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g.in2 + r * g.in2_row), 0, RTI * KI::CHB, 0x00020000);
+    fetch(curA, curB, 0);
+    fetch(curA, curB, 1);
+    // (the lane constants of the synthesis are a dozen selects: formed per plane, they are not carried through the forward phase,
+    // where the 16 accumulator tiles leave no room for them)
+    int qv = q;
+    asm volatile("" : "+v"(qv));
+    const R4Lane r4 = r4_lane(w, qv);
+    double sv = 0.0;
+    commit(0, 0);
+    fetch(curA, curB, 2);
+    // ---- inverse phase ------------------------------------------------------------------------------------------------------------
+    v4d xe[2][2];
+    xe[0][0] = xe[0][1] = xe[1][0] = xe[1][1] = (v4d){0., 0., 0., 0.};
+    v4d tcA = (v4d){0., 0., 0., 0.};
+    static_for<0, RTI>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      if constexpr (c + 1 < RTI) commit(c + 1, (c + 1) % RING);   // (its slot was last read at c - 2, in front of the barrier of c - 1)
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if constexpr (c + 3 < RTI) fetch(curA, curB, c + 3);
+      if constexpr (c == RTI - 3) {
+        // this lane's element of the plane's first (q == 0) or last (q == 3) row, behind the last staged load
+        // (the lane part of the index is formed here, from an opaque copy: hoisted out of the plane loop it is spilled)
+        int lv = lane;
+        asm volatile("" : "+v"(lv));
+        const int qe = lv >> 4;
+        if (g.edge && (qe == 0 || qe == 3))
+          sv = (g.edge + r * g.edge_row + (int64_t)ch * N)[(qe ? g.ppr * N : 0) + 4 * (lv & 15) + w];
+      }
+      unsigned xq = xq0;
+      asm volatile("" : "+v"(xq));
+      constexpr int SB = (c % RING) * KI::CHB;
+      const unsigned pP = (unsigned)r4.eP << 4, pQ = (unsigned)r4.eQ << 4;
+      v4d d2[2];
+      d2[0] = d2[1] = (v4d){0., 0., 0., 0.};
+      constexpr int NF = 2;
+      v2d o[NF][4];
+      r4_issue<0, SB>(o[0], xq, pP, pQ);
+      r4_issue<1, SB>(o[1], xq, pP, pQ);
+      static_for<0, 4>([&](auto tt) {
+        constexpr int t = decltype(tt)::value;
+        constexpr int left = 4 * ((t + NF < 4 ? NF : 4 - t) - 1);
+        v2d (&ot)[4] = o[t % NF];
+        asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(ot[0]), "+v"(ot[1]), "+v"(ot[2]), "+v"(ot[3]) : "n"(left));
+        double Cp, Sp;
+        r4_sums<t == 0>(ot, r4, Cp, Sp);
+        if constexpr (t + NF < 4) {
+          asm volatile("" : "+v"(Cp), "+v"(Sp));
+          r4_issue<t + NF, SB>(ot, xq, pP, pQ);
+        }
+        d2[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(Cp, gzc[t], d2[0], 0, 0, 0);
+        d2[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(Sp, gzs[t], d2[1], 0, 0, 0);
+      });
+      const v4d tc = d2[0] + d2[1];
+      if constexpr ((c & 1) == 0) {
+        tcA = tc;
+      } else {
+        constexpr int cp = c >> 1;
+        v2d f[4];
+        const unsigned fa4 = fx4i ^ (unsigned)(cp << 6);
+#pragma unroll
+        for (int rho = 0; rho < 4; ++rho) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f[rho]) : "v"(fa4), "n"(rho * 4096));
+        const double Ap = tcA[0] + tcA[1], Am = tcA[0] - tcA[1], Bp = tcA[2] + tcA[3], Bm = tcA[2] - tcA[3];
+        const double Pp = tc[0] + tc[1], Pm = tc[0] - tc[1], Qp = tc[2] + tc[3], Qm = tc[2] - tc[3];
+        double Cs[4] = {Ap + Pp, Am + Qm, Ap - Pp, Am - Qm};
+        double Ss[4] = {Bp - Qp, Bm + Pm, Bp + Qp, Bm - Pm};
+        if constexpr (cp == 0) {
+          const bool w0 = q == 0;
+          const double r2 = 1.4142135623730951;
+          Cs[0] = w0 ? Ap + Bp : Cs[0]; Cs[1] = w0 ? Am + Bm : Cs[1]; Cs[2] = w0 ? Ap - Bp : Cs[2]; Cs[3] = w0 ? Am - Bm : Cs[3];
+          Ss[0] = w0 ? r2 * Pp : Ss[0]; Ss[1] = w0 ? Pm + Qm : Ss[1]; Ss[2] = w0 ? r2 * Qp : Ss[2]; Ss[3] = w0 ? Qm - Pm : Ss[3];
+        }
+        static_for<0, 4>([&](auto rr) {
+          constexpr int rho = decltype(rr)::value;
+          asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f[rho]) : "n"(3 - rho));
+          xe[rho >> 1][rho & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].x, Cs[rho], xe[rho >> 1][rho & 1], 0, 0, 0);
+        });
+        static_for<0, 4>([&](auto rr) {
+          constexpr int rho = decltype(rr)::value;
+          xe[rho >> 1][rho & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].y, Ss[rho], xe[rho >> 1][rho & 1], 0, 0, 0);
+        });
+      }
+    });
+    // ---- hand-off: every wave is through with the ring; the plane takes its first 32 KiB -------------------------------------------
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    {
+      unsigned ho = hoff0;
+      asm volatile("" : "+v"(ho));
+#pragma unroll
+      for (int rho = 0; rho < 4; ++rho)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          double val = xe[rho >> 1][rho & 1][rr];
+          if (rho == 0 && rr == 0) val = q == 0 ? sv : val;    // row 0 of the plane
+          if (rho == 3 && rr == 3) val = q == 3 ? sv : val;    // row N - 1
+          *reinterpret_cast<double*>(ring + ((ho ^ (unsigned)(rho << 6)) + rho * 4 * KF::ROWB + rr * KF::CHB)) = val;
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    // ---- forward phase --------------------------------------------------------------------------------------------------------------
+    v4d e2[4][2], o2[4][2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) e2[m][0] = e2[m][1] = o2[m][0] = o2[m][1] = (v4d){0., 0., 0., 0.};
+    static_for<0, RTF>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      unsigned ra = raddr0;
+      asm volatile("" : "+v"(ra));
+      v4d e = (v4d){0., 0., 0., 0.}, o = (v4d){0., 0., 0., 0.};
+      static_for<0, 2>([&](auto hb) {
+        constexpr int t0 = 4 * decltype(hb)::value;
+        v2d a[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(a[t]) : "v"(ra ^ (unsigned)((t0 + t) << 6)), "n"(c * KF::CHB));
+        static_for<0, 4>([&](auto tt) {
+          constexpr int t = decltype(tt)::value;
+          asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[t]) : "n"(3 - t));
+          e = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t].x, gE[t0 + t], e, 0, 0, 0);
+          o = __builtin_amdgcn_mfma_f64_16x16x4f64(a[t].y, gO[t0 + t], o, 0, 0, 0);
+        });
+      });
+      const v4d tp = e + o, tm = e - o;
+      v2d f[4];
+      const unsigned fa4 = fx4f ^ (unsigned)(c << 6);
+#pragma unroll
+      for (int rho = 0; rho < 4; ++rho) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f[rho]) : "v"(fa4), "n"(rho * 4096));
+      static_for<0, 4>([&](auto rr) {
+        constexpr int rho = decltype(rr)::value;
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f[rho]) : "n"(3 - rho));
+        e2[rho][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].x, tp[rho], e2[rho][0], 0, 0, 0);
+        e2[rho][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].x, tm[rho], e2[rho][1], 0, 0, 0);
+        o2[rho][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].y, tp[rho], o2[rho][0], 0, 0, 0);
+        o2[rho][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].y, tm[rho], o2[rho][1], 0, 0, 0);
+      });
+    });
+    // every wave has read the plane: the next plane's chunks may take the ring (the stores below run beside them)
+    asm volatile("s_barrier" ::: "memory");
+    char* const op4 = reinterpret_cast<char*>(g.out + r * g.out_row + ch * g.out_plane) + soff;
+    const bool w0 = q == 0;
+    const double r2 = 1.4142135623730951;
+    static_for<0, 4>([&](auto rr_) {
+      constexpr int rr = decltype(rr_)::value;
+      __builtin_amdgcn_sched_barrier(0);
+      v2d u0, u1, v0, v1, ws, wd, z0, z1;
+#pragma unroll
+      for (int v = 0; v < 2; ++v) {
+        u0[v] = e2[0][v][rr] + e2[2][v][rr]; u1[v] = e2[0][v][rr] - e2[2][v][rr];
+        v0[v] = e2[1][v][rr] + e2[3][v][rr]; v1[v] = e2[1][v][rr] - e2[3][v][rr];
+        ws[v] = o2[0][v][rr] + o2[2][v][rr]; wd[v] = o2[0][v][rr] - o2[2][v][rr];
+        z0[v] = o2[1][v][rr] + o2[3][v][rr]; z1[v] = o2[1][v][rr] - o2[3][v][rr];
+      }
+      char* const rowp = op4 + (size_t)(32 * rr) * out_rowB;
+      auto put = [&](int k, v2d val) {
+        if constexpr (XZF_CF_NT_ST) __builtin_nontemporal_store(val, reinterpret_cast<v2d*>(rowp + (size_t)k * out_rowB));
+        else *reinterpret_cast<v2d*>(rowp + (size_t)k * out_rowB) = val;
+      };
+      put(0, u0 + v0);
+      put(1, u0 - v0);
+      if constexpr (rr == 0) {
+        const v2d a0 = (v2d){r2 * o2[0][0][rr], r2 * o2[0][1][rr]}, a2 = (v2d){r2 * o2[2][0][rr], r2 * o2[2][1][rr]};
+        put(2, w0 ? u1 + v1 : ws + z0);
+        put(3, w0 ? u1 - v1 : ws - z0);
+        put(4, w0 ? a0 + z1 : u1 + z1);
+        put(5, w0 ? a0 - z1 : u1 - z1);
+        put(6, w0 ? a2 + z0 : v1 - wd);
+        put(7, w0 ? a2 - z0 : -wd - v1);
+      } else {
+        put(2, ws + z0);
+        put(3, ws - z0);
+        put(4, u1 + z1);
+        put(5, u1 - z1);
+        put(6, v1 - wd);
+        put(7, -wd - v1);
+      }
+    });
+  }
+}
+
 // ---- lattice Gram, x step + eigenvalue scaling + channel sum (folded form of xcorr_kernel in xz2d.hip) -------------------------
 // For every (row r, y-mode p) plane X (N x N, x rows, z contiguous):   out[r][p][o] = sum_z lamT[p][z][o] * sum_x G_x[o][x] X[x][z].
 // The product is formed transposed (D[z][o]: the z sum then runs over accumulator registers and the four 16-lane groups).
@@ -993,6 +1292,18 @@ int launch_inv(const FoldArgs& g, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }
 
+int launch_conv_fwd(const FoldArgs& g, hipStream_t st) {
+  using K = ConvFwdCfg<64, XZF_CF_RING>;
+  auto kern = xz_conv_fwd_kernel<64, XZF_CF_RING>;
+  static std::atomic<uint64_t> attr_done{0};
+  if (int rc = ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), K::LDS)) return rc;
+  // persistent, plane-strided, as launch_fwd / launch_inv (512 and 1024 workgroups, and a start-up stagger of every other one,
+  // measured the same to 1 %)
+  const int64_t nwg = g.nplanes < 2048 ? g.nplanes : 2048;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), K::LDS, st, g);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
+
 // dense planes: the right half of a row and the bottom rows follow in place
 void dense_fwd(FoldArgs& g, int n) { g.in_rowB = n * 8; g.in_halfB = n * 4; g.in_botB = 0; g.out_rowB = 2 * n * 8; g.out_halfB = n * 8; g.out_botB = 0; }
 void dense_inv(FoldArgs& g, int n) { g.in_rowB = 2 * n * 8; g.in_halfB = n * 8; g.in_botB = 0; g.out_rowB = 0; g.out_halfB = n * 4; g.out_botB = 0; }
@@ -1144,4 +1455,22 @@ extern "C" int geobo_xz2d_fold_inv_mul(int n, int64_t rows, int planes_per_row, 
   g.in2 = b; g.in2_row = b_row; g.r2_first = 0; g.ss = nullptr;
   dense_inv(g, 64);
   return launch_inv<64, 2>(g, (hipStream_t)stream);
+}
+
+extern "C" int geobo_xz2d_fold_conv_fwd(int n, int64_t rows, int planes_per_row, const double* a, int64_t a_plane, const double* b,
+                                        int64_t b_row, const double* slab, int64_t slab_row, const double* Fx, const double* Fz,
+                                        double* out, int64_t out_row, int64_t out_plane, void* stream) {
+  if (!a || !b || !out || !Fx || !Fz) return GEOBO_E_ARG;
+  if (rows <= 0 || planes_per_row <= 0) return GEOBO_OK;
+  if ((a_plane & 1) || (b_row & 1) || (out_row & 1) || (out_plane & 1) || ((uintptr_t)a & 15) || ((uintptr_t)b & 15) ||
+      ((uintptr_t)out & 15) || ((uintptr_t)slab & 7) || ((uintptr_t)Fx & 15) || ((uintptr_t)Fz & 15))
+    return GEOBO_E_ALIGN;
+  if (n != 64) return GEOBO_E_UNSUPPORTED;
+  FoldArgs g;
+  g.in = a; g.in_row = 0; g.in_plane = a_plane; g.out = out; g.out_row = out_row; g.out_plane = out_plane; g.out_rs = n;
+  g.Fz = Fz; g.Fx = Fx; g.ppr = planes_per_row; g.nplanes = rows * planes_per_row;
+  g.row_off = nullptr; g.edge = slab; g.edge_row = slab_row;
+  g.in2 = b; g.in2_row = b_row; g.r2_first = 0; g.ss = nullptr;
+  dense_fwd(g, 64);
+  return launch_conv_fwd(g, (hipStream_t)stream);
 }

@@ -210,6 +210,9 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         # operator build measured and what the last step did with it -- dict(deviation, bound, symmetric, taken); _mirror: (operator, symmetric)
         self.aka_mirror_on = os.environ.get("GEOBO_AKA_MIRROR", "1") != "0"
         self.aka_mirror, self._mirror, self._mirror_meas = {}, {}, None
+        # Rows of L^-1 A enter the posterior's covariance product as spectra, Z is never stored (transposed._posterior_zpath; DESIGN.md
+        # section 2 item 4): GEOBO_Z_SPECTRUM=0 restores the stored rows.  Resolved here like GEOBO_AKA_MIRROR, for the same reason
+        self.z_spectrum_on = os.environ.get("GEOBO_Z_SPECTRUM", "1") != "0"
         # Row form (plan.Route.family "rows", rowform.py): statically possible; whether a step takes it is decided when the operators
         # are built (lattice survey, even stencils).  Column form from 4 ranks: row-sharded transforms + one all-to-all of A K block
         # columns per operator (with 2 ranks the exchange would move a quarter of A K over ONE xGMI link, more than the forward passes

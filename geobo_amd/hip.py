@@ -159,6 +159,20 @@ def xz2d_fold_inv_mul(n, rows, ppr, a, a_plane, b, b_row, Fx, Fz, out, out_row, 
                                            int(out_rowstride), _stream()), "geobo_xz2d_fold_inv_mul")
 
 
+def xz2d_fold_conv_fwd(n, rows, ppr, a, a_plane, b, b_row, slab, slab_row, Fx, Fz, out, out_row, out_plane):
+    """Forward radix-2 spectrum of the inverse transform of the planes a[p] * b[r], rows 0 and n - 1 of every plane taken from
+    slab[r][k][p][n] (None: zeros); the planes themselves are never stored (geobo_xz2d_fold_conv_fwd)."""
+    lib = require_gpu()
+    P = 4 * n * n
+    room = lambda t, name: _chk(t, name).untyped_storage().nbytes() // 8 - t.storage_offset()      # doubles behind the first element
+    assert room(a, "a") >= (ppr - 1) * a_plane + P and room(b, "b") >= (rows - 1) * b_row + P
+    assert room(out, "out") >= (rows - 1) * out_row + (ppr - 1) * out_plane + P
+    assert slab is None or room(slab, "slab") >= (rows - 1) * slab_row + 2 * ppr * n
+    _lib.check(lib.geobo_xz2d_fold_conv_fwd(int(n), int(rows), int(ppr), _p(a), int(a_plane), _p(b), int(b_row),
+                                            _p(slab) if slab is not None else None, int(slab_row), _p(_chk(Fx, "Fx")), _p(_chk(Fz, "Fz")),
+                                            _p(out), int(out_row), int(out_plane), _stream()), "geobo_xz2d_fold_conv_fwd")
+
+
 def colgemv(X, v, out=None, ws=None):
     """out[c] = sum_r X[r, c] v[r]  (X: 2-D row-major CUDA float64, unit column stride, even width)."""
     lib = require_gpu()

@@ -207,6 +207,32 @@ class PooledRows:
         return PooledRows(self.pool, self.row_off, self.edge, self.jy, self.jx, self.r0 + r0, self.geo)
 
 
+class ConvolvedRows:
+    """Rows of L^-1 A of a lattice survey that are never materialised, for products whose Toeplitz axis is z (nx = ny = nz = 64): row r
+    is the lattice convolution of Lview[r] (a sensor image, ny x nx) with the operator's stencil table, given by its eigen-data
+    lam3[iz][ky][kx] (LatticeGram.transpose_tables3), boundary slabs iy = 0, ny - 1 apart in slab[r][k][iz][ix] (LatticeGram.
+    edge_apply_transpose(..., zx=True)).  spectrum() hands the (y, x)-spectrum of every z channel to the y stage in ONE launch per batch
+    (geobo_xz2d_fold_conv_fwd): the voxel-domain row is never written."""
+
+    def __init__(self, gram, Lview, lam3, slab, r0=0):
+        self.gram, self.Lview, self.lam3, self.slab, self.r0 = gram, Lview, lam3, slab, int(r0)
+
+    def rows(self, r0):
+        return ConvolvedRows(self.gram, self.Lview, self.lam3, self.slab, self.r0 + r0)
+
+    def spectrum(self, sp, R, out_name):
+        """[R][nz][Cp] planes (ky, kx) of the first R rows into sp's work buffer `out_name`."""
+        nx, ny, nz, Px, Py, Cp = sp.nx, sp.ny, sp.nz, sp.Px, sp.Py, sp.Cp
+        assert nx == ny == nz == 64 and Cp >= Py * Px
+        a = self.r0
+        lh = sp.buf("LG_Lh", R * Py * Px)
+        self.gram._plane_yx(False, R, self.Lview[a:], self.Lview.stride(0), lh, Py * Px)
+        t2 = sp.buf(out_name, R * nz * Cp)
+        hip.xz2d_fold_conv_fwd(ny, R, nz, self.lam3, Py * Px, lh, Py * Px, self.slab[a:], self.slab.stride(0), sp.F["y"], sp.F["x"],
+                               t2, nz * Cp, Cp)
+        return t2
+
+
 class SpectralProduct:
     """AK rows by the real-DFT route for one grid; holds the transform matrices and the work buffers."""
 
@@ -385,9 +411,12 @@ class SpectralProduct:
         return outs, outs2
 
     def _rows_spectrum(self, A, r0, R, out_name):
-        """(x, z)-spectrum of the rows r0 .. r0 + R of an operand: tensor rows, LatticeRows or PooledRows (nothing to transform)."""
+        """(x, z)-spectrum of the rows r0 .. r0 + R of an operand: tensor rows, LatticeRows, PooledRows (nothing to transform) or
+        ConvolvedRows (the (y, x)-spectrum of every z channel: the product's Toeplitz axis is z)."""
         if isinstance(A, PooledRows):
             return A.rows(r0)
+        if isinstance(A, ConvolvedRows):
+            return A.rows(r0).spectrum(self, R, out_name)
         if isinstance(A, LatticeRows):
             return self.forward_zx(A.rows(r0), R, self.G, out_name=out_name)
         return self.forward_zx(A[r0:], R, self.G, src_row_stride=A.stride(0), out_name=out_name)
@@ -558,12 +587,18 @@ class SpectralProduct:
         """The part of flops() executed on the fp64 VALU (the y stage's vector-pipe work); everything else is MFMA."""
         return rows * self.y_stage_flop(1, nblocks, slab)[1] if self.dense_y else 0.0
 
-    def eigenvalues(self, table_mirrored):
+    def eigenvalues(self, table_mirrored, toeplitz_z=False):
         """What product() needs of one covariance block, from the (z-mirrored) lattice table of geobo_cov_table:
         dense-y route: the Toeplitz generators t[d][ox][oz] = (E_x E_z k)(d, ox, oz) / (Px Pz)   ([ny][Px*Pz]);
-        otherwise the full eigenvalue cube Lambda'/(Py Px Pz) on the G row index."""
+        otherwise the full eigenvalue cube Lambda'/(Py Px Pz) on the G row index.
+        toeplitz_z (dense-y route, nx = ny = nz): the half table k(dy, dx, dz) is permuted to [dz][dy][dx] first -- generators
+        t[dz][oy][ox] of a product whose Toeplitz axis is z and whose planes are (y, x) (ConvolvedRows).  The TABLE is permuted, no
+        isotropy is assumed: unequal voxel sizes stay exact; the transform matrices of equal extents are identical."""
         nx, ny, nz = self.nx, self.ny, self.nz
         T = table_mirrored[:ny * nx * 2 * nz].view(ny, nx, 2 * nz)[:, :, nz - 1:2 * nz - 1].contiguous()
+        if toeplitz_z:
+            assert self.dense_y and nx == ny == nz
+            T = T.permute(2, 0, 1).contiguous()
         src = self.buf("Tsrc", self.N)
         src[:self.N] = T.reshape(-1)
         if self.dense_y:

@@ -98,6 +98,12 @@ class TransposedPosteriorMixin:
             gram.apply_transpose_zx(Lview, nrows, hit[1], out)      # rows as [iy][iz][ix]
         else:
             gram.apply_transpose(Lview, nrows, hit[1], out)
+        self._lattice_slabs(Lview, nrows, func, A, [out[:, iy * pl:(iy + 1) * pl] for iy in (0, ny - 1)], zx=zx, edge=edge)
+
+    def _lattice_slabs(self, Lview, nrows, func, A, outs, zx=False, edge=None):
+        """The two boundary slabs iy = 0, ny - 1 of the rows of _lattice_Z into outs[0], outs[1] ((>= nrows x nx*nz) views), through the
+        slabs' x-DFT spectra (lattice_gram.edge_apply_transpose)."""
+        gram, pl, ny = self._gram, self.nx * self.nz, self.ny
         for k, iy in enumerate((0, ny - 1)):
             if edge is not None:                      # (row form: the two boundary slabs of every sensor, engine.operator)
                 ycols = edge[k]
@@ -111,7 +117,28 @@ class TransposedPosteriorMixin:
             vt = self._edgeVt.get(key)
             if vt is None or vt[0] != ycols.data_ptr():
                 vt = self._edgeVt[key] = (ycols.data_ptr(), gram.edge_eigen_t(ycols))
-            gram.edge_apply_transpose(Lview, nrows, vt[1], out[:, iy * pl:(iy + 1) * pl], zx=zx)
+            gram.edge_apply_transpose(Lview, nrows, vt[1], outs[k], zx=zx)
+
+    def _z_spectrum_ok(self):
+        """Rows of L^-1 A enter the posterior's covariance product as spectra (spectral.ConvolvedRows; GEOBO_Z_SPECTRUM, default on):
+        the zx form of the lattice application with the product formed inside the inverse kernel, the squaring inverse fused, the y
+        stage on the matrix pipe with the one-pass two-term join."""
+        sp = self._spectral
+        f = sp.forms
+        return bool(self.z_spectrum_on and f.zx and f.z_mul and sp.fused_ss() and sp.y_mfma and f.y_two_term == "y2t")
+
+    def _convolved_rows(self, Lview, nrows, func, A):
+        """spectral.ConvolvedRows of  Lview A  (the rows _lattice_Z(..., zx=True) would store): only their boundary slabs are computed
+        here, 64 KB per row, into a compact buffer [row][k][iz][ix] of the operator's own."""
+        from .spectral import ConvolvedRows
+        gram, pl = self._gram, self.nx * self.nz
+        lam = self._lam[func][1]
+        hit = self._lamW.get((func, True))
+        if hit is None or hit[0] is not lam:
+            hit = self._lamW[(func, True)] = (lam, gram.transpose_tables3(lam))
+        slab = self._workspace2d("Zslab_" + func, nrows, 2 * pl)
+        self._lattice_slabs(Lview, nrows, func, A, [slab[:, k * pl:(k + 1) * pl] for k in (0, 1)], zx=True)
+        return ConvolvedRows(gram, Lview, hit[1], slab)
 
     def _posterior_zpath(self, step, Linv, AK, u, A_g, A_m):
         """Posterior mean and variance in the TRANSPOSED order (round 3).  V = L^-1 (A3 K) is (L^-1 A3) K as well, and A3 is block
@@ -128,21 +155,32 @@ class TransposedPosteriorMixin:
         nx, ny, nz = self.nx, self.ny, self.nz
         cws = self._workspace("colgemv_ws", (max(hip.colgemv_ws_doubles(M_pad, M_pad), hip.colgemv_ws_doubles(Msp, self.N_pad)),))
         w = self._timed("posterior_mean", 0.0, lambda: hip.colgemv(Linv, u, ws=cws))
-        Zg, Zm = self._workspace2d("Zg", 2 * Msp, N), self._workspace2d("Zm", Msp, N)
+        Zg = Zm = None
+        zs = False
         # Z = L^-1[:, operator columns] A: on a lattice survey a (y, x) convolution of every row's sensor image with the operator's
         # stencil table (lattice_gram.apply_transpose: 2e8 flop per row), otherwise two triangular MFMA GEMMs (2.1e9 flop per row)
         lat = (self._gram is not None and self._gram.edge_supported() and Msp == nx * ny and self.route.opt("z_lattice")
                and all(self._lam.get(f) is not None and self._lam[f][0] is A for f, A in (("grav", A_g), ("magn", A_m))))
         if lat:
             gram = self._gram
-            fl = 3 * Msp * (gram.flops(1, ny) + 2 * 3 * 2.0 * 128 * 128 * 64)
+            fl_conv, fl_slab = 3 * Msp * gram.flops(1, ny), 3 * Msp * 2 * 3 * 2.0 * 128 * 128 * 64
 
             zx = gram.zx_supported()          # rows of Z as [iy][iz][ix]: the fused inverse transform writes them, the products below follow
+            # ... or not at all: the covariance product takes z as its Toeplitz axis, and the (iy, ix) plane the convolution produces per
+            # (row, iz) goes through the product's forward transform inside the same kernel (spectral.ConvolvedRows).  Only the
+            # boundary slabs are computed ahead of the product
+            zs = zx and self._z_spectrum_ok()
 
             def zlattice():
+                nonlocal Zg, Zm
+                if zs:
+                    Zg = self._convolved_rows(Linv[:2 * Msp, :Msp], 2 * Msp, "grav", A_g)
+                    Zm = self._convolved_rows(Linv[Msp:2 * Msp, Msp:2 * Msp], Msp, "magn", A_m)
+                    return
+                Zg, Zm = self._workspace2d("Zg", 2 * Msp, N), self._workspace2d("Zm", Msp, N)
                 self._lattice_Z(Linv[:2 * Msp, :Msp], 2 * Msp, "grav", A_g, Zg, zx=zx)
                 self._lattice_Z(Linv[Msp:2 * Msp, Msp:2 * Msp], Msp, "magn", A_m, Zm, zx=zx)
-            self._timed("posterior_zlattice", fl, zlattice)
+            self._timed("posterior_zlattice", fl_slab if zs else fl_conv + fl_slab, zlattice)
             Ag = Am = None
             vec_of = lambda func, wv, out: self._lattice_Z(wv.view(1, -1), 1, func, A_g if func == "grav" else A_m, out)
         else:
@@ -152,6 +190,8 @@ class TransposedPosteriorMixin:
             fl = 2.0 * N * (2 * tri + 1.0 * Msp * Msp)
             alg = 2.0 * N * (2 * (Msp * (Msp + 1) / 2.0) + 1.0 * Msp * Msp)
 
+            Zg, Zm = self._workspace2d("Zg", 2 * Msp, N), self._workspace2d("Zm", Msp, N)
+
             def zgemm():
                 hip.gemm_nn(Linv[:2 * Msp, :Msp], Ag[:Msp, :N], Zg, x_lower=True)
                 hip.gemm_nn(Linv[Msp:2 * Msp, Msp:2 * Msp], Am[:Msp, :N], Zm, x_lower=True)
@@ -159,10 +199,11 @@ class TransposedPosteriorMixin:
             vec_of = lambda func, wv, out: hip.colgemv((Ag if func == "grav" else Am)[:Msp, :N], wv, out=out[0], ws=cws)
         mu_l = self._timed("posterior_mean", 0.0, lambda: self._mean_rows(step, w, vec_of)).reshape(-1)
         zx = lat and zx
-        ss, tg, tm, y2s, voxel_order = self._ss_cubes(step, zx)
+        zs = zx and zs
+        ss, tg, tm, y2s, voxel_order = self._ss_cubes(step, zx, toeplitz_z=zs)
         shared = y2s is not None and P_c == 2
-        self._timed("posterior_spectral", sp.flops_ss(Msp, Msp, P_c, shared), lambda: sp.reduce_ss(Zg, 2 * Msp, tg, Zm, Msp, tm, ss, y2s=y2s),
-                    valu=sp.valu_ss(Msp, Msp, P_c, shared))
+        self._timed("posterior_spectral", sp.flops_ss(Msp, Msp, P_c, shared) + (fl_conv if zs else 0.0),
+                    lambda: sp.reduce_ss(Zg, 2 * Msp, tg, Zm, Msp, tm, ss, y2s=y2s), valu=sp.valu_ss(Msp, Msp, P_c, shared))
         ssum = torch.stack([voxel_order(t) for t in ss])                                  # (P_c, N)
         if Md:
             # K_2j[drill voxels, :]: the drill rows of A K, already there (fp64, every voxel column: _zpath_ok), zero rows behind them
@@ -172,16 +213,22 @@ class TransposedPosteriorMixin:
                 Kd=Kd, y2s=None if zx else y2s))             # (zx: y2s holds the tables of the transposed planes)
         return mu_l, (amp * 1.0 - ssum).reshape(-1)
 
-    def _ss_cubes(self, step, zx):
+    def _ss_cubes(self, step, zx, toeplitz_z=False):
         """What both transposed posteriors hand to sp.reduce_ss, and the way back: (ss, tg, tm, y2s, voxel_order).  ss: the zeroed partial
         cubes post_ss_* (sp.ss_slots() slots per block); tg / tm: the step's generators of the blocks (0, j) / (1, j), as tables of
         transposed planes where the rows of Z come as [iy][iz][ix] (zx); y2s: their three-product tables -- blocks (0, 1) and (1, 0) of
         a symmetric prior coincide: three y-stage products per two-term row instead of four.  voxel_order(t): one block's cube summed
-        over its slots, N values in voxel order (iy, ix, iz)."""
+        over its slots, N values in voxel order (iy, ix, iz).
+        toeplitz_z: the rows are spectral.ConvolvedRows -- generators of the permuted tables (one single-row transform per block:
+        sp.eigenvalues(..., toeplitz_z=True)), cubes come back as [iz][iy][ix]."""
         props, sp, nx, ny, nz = step.props, self._spectral, self.nx, self.ny, self.nz
         ss = [self._workspace("post_ss_%d" % jj, (sp.ss_slots(), ny, nx * nz)) for jj in range(len(props))]
         for t in ss:
             t.zero_()
+        if toeplitz_z:
+            tg, tm = ([sp.eigenvalues(step.prior.table(self, s_, j), toeplitz_z=True) for j in props] for s_ in (0, 1))
+            y2s = sp.y2s_tables(tg, tm) if tuple(props[:2]) == (0, 1) else None
+            return ss, tg, tm, y2s, lambda t: t.sum(0).view(nz, ny, nx).permute(1, 2, 0).reshape(-1)
         swap = (lambda g: g.view(ny, sp.Px, sp.Pz).transpose(1, 2).contiguous().view(-1)) if zx else (lambda g: g)
         tg, tm = [swap(step.gens[(0, j)]) for j in props], [swap(step.gens[(1, j)]) for j in props]
         y2s = sp.y2s_tables(tg, tm) if tuple(props[:2]) == (0, 1) else None

@@ -350,6 +350,16 @@ int geobo_xz2d_fold_inv_mul(int n, int64_t rows, int planes_per_row, const doubl
                             const double* Fx, const double* Fz, double* out, int64_t out_row, int64_t out_plane,
                             int64_t out_rowstride, void* stream);
 
+/* geobo_xz2d_fold_inv_mul followed by the forward transform geobo_xz2d_fold of every plane it produces, in ONE kernel: the n x n plane
+ * (r, p) = inverse transform of a[p] * b[r] never leaves the chip -- it is handed from the inverse's accumulators through LDS to the
+ * forward transform, whose 2n x 2n spectrum goes to out + r*out_row + p*out_plane (dense rows).  The first and the last ROW of
+ * every plane are replaced before the forward transform by slab[r*slab_row + k*planes_per_row*n + p*n + (0 .. n-1)], k = 0 / 1
+ * (the boundary slabs of the transposed lattice application, which do not come from the stencil table); slab == NULL: zeros.
+ * Same sums in the same order as the two launches.  n = 64. */
+int geobo_xz2d_fold_conv_fwd(int n, int64_t rows, int planes_per_row, const double* a, int64_t a_plane, const double* b, int64_t b_row,
+                             const double* slab, int64_t slab_row, const double* Fx, const double* Fz, double* out, int64_t out_row,
+                             int64_t out_plane, void* stream);
+
 /* geobo_xz2d_fold for planes of HALF the extent (n = 32) on the n = 64 kernels: a group of four consecutive planes y .. y+3 of a row is one
  * kernel plane [[y, y+1], [y+2, y+3]] (the kernel reads / writes half-length memory rows; right half and bottom rows come from the
  * neighbouring planes), Fx / Fz are the folded matrices of diag(G_32, G_32) ((64, 32, 2)): four independent transforms per kernel

@@ -109,7 +109,7 @@ if which in ("all", "xcorr"):
           lambda: hip.xcorr_reduce(n, n, R, P, src, src.stride(0), n * n, Gx, lam, out, out.stride(0), P))
 # ---- radix-2 / radix-4 kernels: flop = what the folded kernels execute on the matrix pipe (forward: half of the plain product along z,
 # a quarter along x; inverse and xcorr_fold: a quarter) -----------------------------------------------------------------
-if which in ("all", "fold_fwd", "fold_bwd", "xcorr_fold", "fold_inv_ss", "fold_inv_strided", "fold_inv_mul"):
+if which in ("all", "fold_fwd", "fold_bwd", "xcorr_fold", "fold_inv_ss", "fold_inv_strided", "fold_inv_mul", "fold_conv_fwd", "fold_conv_pair"):
     import numpy as np
     from geobo_amd.spectral import folded_matrices
     F = hip.to_dev(np.stack(folded_matrices(n), axis=2))
@@ -206,3 +206,21 @@ if which in ("all", "fold_inv_mul"):
     timed("xz2d_fold_inv_mul", R * n * 0.5 * (P * P * n + n * P * n), (n * P * P + R * P * P + R * n * n * n) * 8.0,
           lambda: hip.xz2d_fold_inv_mul(n, R, n, lam3, P * P, lh, P * P, F, F, out, out.stride(0), n, n * n))
     del lam3, lh, out
+if which in ("all", "fold_conv_fwd", "fold_conv_pair"):
+    # rows of L^-1 A as spectra: the same product-input inverse carried straight through the forward transform of every plane
+    # (geobo_xz2d_fold_conv_fwd: the 64 x 64 planes never leave the chip), and the pair of launches it replaces (the voxel-domain rows
+    # written and read back); boundary rows from a compact slab buffer [row][2][iz][ix]
+    lam3, lh, slab = rnd(n * P * P), rnd(R * P * P), rnd(R, 2 * n * n)
+    spec = torch.empty(R * n * P * P, dtype=torch.float64, device=dev)
+    flop = R * n * (0.5 * (P * P * n + n * P * n) + 1.0 * (n * n * P + 0.5 * P * n * P))
+    if which in ("all", "fold_conv_fwd"):
+        timed("xz2d_fold_conv_fwd", flop, (n * P * P + R * P * P + R * 2 * n * n + R * n * P * P) * 8.0,
+              lambda: hip.xz2d_fold_conv_fwd(n, R, n, lam3, P * P, lh, P * P, slab, slab.stride(0), F, F, spec, n * P * P, P * P))
+    if which in ("all", "fold_conv_pair"):
+        Z = torch.empty((R, n * n * n), dtype=torch.float64, device=dev)
+        def pair():
+            hip.xz2d_fold_inv_mul(n, R, n, lam3, P * P, lh, P * P, F, F, Z, Z.stride(0), n, n * n)
+            hip.xz2d_fold(False, n, R, n, Z, Z.stride(0), n * n, F, F, spec, n * P * P, P * P)
+        timed("xz2d_fold_inv_mul + xz2d_fold", flop, (n * P * P + R * P * P + 2 * R * n * n * n + R * n * P * P) * 8.0, pair)
+        del Z
+    del lam3, lh, slab, spec
