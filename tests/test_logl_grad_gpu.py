@@ -31,6 +31,7 @@ def _loaded(name, kern, shape=TINY, **kw):
 # ---- 1. derivative covariance ids --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["exp", "matern32", "sparse"])
 def test_k_eval_derivatives_against_central_differences(name):
+    # the by-value check of the same ids (multiprecision reference, envelope units) is tests/test_covfun_gpu.py
     from geobo_amd import hip
     from oracle import geobo_oracle as O
     l1, l2 = 200.0, 230.0
