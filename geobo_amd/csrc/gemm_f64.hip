@@ -665,6 +665,41 @@ __global__ void posterior_finish_kernel(const double* part_mu, const double* par
   var[c] = prior_var - s;
 }
 
+// Workgroup -> tile map of a launch and the grid that goes with it: the ONE place where the choice is made (launch() below and
+// the host query geobo_gemm_map both call it).  batch >= 1.
+struct MapChoice { int xcd_map, ntiles, nblocks, grid_y; };
+inline MapChoice choose_map(int ymode, int epi, int nbi, int nbj, int tm, int tn, int tri, int batch) {
+  MapChoice c;
+  c.xcd_map = (nbi >= 8) ? 1 : 0;
+  // supertiles help when both operands stream (measured: posterior_reduce 59 -> 66 TF/s); with lower_only skipping they
+  // unbalance the tail (AkA 420 -> 499 ms), so triangular-output launches keep the row-per-XCD map
+  if (mem_mode(ymode) && !(tri & TRI_LOWER_ONLY) && nbi >= 4 && nbj >= 8) c.xcd_map = 2;
+  c.ntiles = 0;
+  const int64_t items = (int64_t)nbi * nbj * batch;
+  // up to a few dozen tiles per CU: the tail of the launch matters -> balanced item list (plain and lower_only NT/NN)
+  // (also the triangular-operand merges of the L^-1 build: longest contraction ranges first, equal lengths together)
+  if (mem_mode(ymode) && epi == EPI_STORE && batch <= 64 &&
+      nbi * nbj >= ((tri & (TRI_X_LOWER | TRI_Y_LOWER)) ? 16 : 64) && items <= 65536 && nbi <= 4096 &&
+      (tri & (TRI_X_LOWER | TRI_Y_LOWER)) != (TRI_X_LOWER | TRI_Y_LOWER)) {
+    c.ntiles = (int)tile_items(nbi, nbj, tm, tn, tri);
+    if (c.ntiles > 0) c.xcd_map = 3;
+  }
+  c.nblocks = nbi * nbj;
+  c.grid_y = batch;
+  if (c.xcd_map == 3) {       // 1-D grid over (batch, tile) items, whole groups of 32 items on all 8 XCDs
+    const int64_t groups = ((int64_t)c.ntiles * batch + 31) / 32;
+    c.nblocks = (int)(8 * 32 * ((groups + 7) / 8));
+    c.grid_y = 1;
+  }
+  if (c.xcd_map == 1) c.nblocks = 8 * ((nbi + 7) / 8) * nbj;
+  if (c.xcd_map == 2) {
+    int nst = ((nbi + 3) / 4) * ((nbj + 7) / 8);
+    if (tri & TRI_X_LOWER) nst = nbi * ((nbj + 31) / 32);
+    c.nblocks = 8 * 32 * ((nst + 7) / 8);
+  }
+  return c;
+}
+
 template <int WM, int WN, int YMODE, int EPI, int KID>
 int launch(GemmArgs& a, hipStream_t st) {
   constexpr int NT = 64 * WM * WN;
@@ -681,35 +716,11 @@ int launch(GemmArgs& a, hipStream_t st) {
   }
   if (a.m_valid <= 0) a.m_valid = (int64_t)1 << 62;
   if (a.n_valid <= 0) a.n_valid = (int64_t)1 << 62;
-  a.xcd_map = (a.nbi >= 8) ? 1 : 0;
-  // supertiles help when both operands stream (measured: posterior_reduce 59 -> 66 TF/s); with lower_only skipping they
-  // unbalance the tail (AkA 420 -> 499 ms), so triangular-output launches keep the row-per-XCD map
-  if (mem_mode(YMODE) && !(a.tri & TRI_LOWER_ONLY) && a.nbi >= 4 && a.nbj >= 8) a.xcd_map = 2;
-  a.ntiles = 0;
   if (a.batch <= 0) a.batch = 1;
-  const int64_t items = (int64_t)a.nbi * a.nbj * a.batch;
-  // up to a few dozen tiles per CU: the tail of the launch matters -> balanced item list (plain and lower_only NT/NN)
-  // (also the triangular-operand merges of the L^-1 build: longest contraction ranges first, equal lengths together)
-  if (mem_mode(YMODE) && EPI == EPI_STORE && a.batch <= 64 &&
-      a.nbi * a.nbj >= ((a.tri & (TRI_X_LOWER | TRI_Y_LOWER)) ? 16 : 64) && items <= 65536 && a.nbi <= 4096 &&
-      (a.tri & (TRI_X_LOWER | TRI_Y_LOWER)) != (TRI_X_LOWER | TRI_Y_LOWER)) {
-    a.ntiles = (int)tile_items(a.nbi, a.nbj, 64 * WM, 64 * WN, a.tri);
-    if (a.ntiles > 0) a.xcd_map = 3;
-  }
-  int nblocks = a.nbi * a.nbj;
-  if (a.xcd_map == 3) {
-    const int64_t groups = ((int64_t)a.ntiles * a.batch + 31) / 32;
-    nblocks = (int)(8 * 32 * ((groups + 7) / 8));
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(NT), lds, st, a);
-    return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
-  }
-  if (a.xcd_map == 1) nblocks = 8 * ((a.nbi + 7) / 8) * a.nbj;
-  if (a.xcd_map == 2) {
-    int nst = ((a.nbi + 3) / 4) * ((a.nbj + 7) / 8);
-    if (a.tri & TRI_X_LOWER) nst = a.nbi * ((a.nbj + 31) / 32);
-    nblocks = 8 * 32 * ((nst + 7) / 8);
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks, a.batch), dim3(NT), lds, st, a);
+  const MapChoice c = choose_map(YMODE, EPI, a.nbi, a.nbj, 64 * WM, 64 * WN, a.tri, a.batch);
+  a.xcd_map = c.xcd_map;
+  a.ntiles = c.ntiles;
+  hipLaunchKernelGGL(kern, dim3(c.nblocks, c.grid_y), dim3(NT), lds, st, a);
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }
 
@@ -738,7 +749,17 @@ extern "C" int64_t geobo_tile_order(int nbi, int nbj, int tm, int tn, int lower_
   return n;
 }
 
-extern "C" int geobo_ak_fused(int kernel_id, const double* A, int64_t Ms_pad, int64_t N_pad, int64_t lda,
+extern "C" int geobo_gemm_map(int ymode, int reduce_epilogue, int nbi, int nbj, int tm, int tn, int tri_flags, int batch,
+                              int* out) {
+  if (!out || ymode < Y_GEN || ymode > Y_NT_XT || nbi <= 0 || nbj <= 0 || (tm != 128 && tm != 256) || tn != 128 || batch <= 0 ||
+      (tri_flags & ~(TRI_LOWER_ONLY | TRI_X_LOWER | TRI_Y_LOWER)))
+    return GEOBO_E_ARG;
+  const MapChoice c = choose_map(ymode, reduce_epilogue ? EPI_REDUCE : EPI_STORE, nbi, nbj, tm, tn, tri_flags, batch);
+  out[0] = c.xcd_map; out[1] = c.ntiles; out[2] = c.nblocks; out[3] = c.grid_y;
+  return GEOBO_OK;
+}
+
+extern "C" int geobo_ak_fused(int kernel_id,const double* A, int64_t Ms_pad, int64_t N_pad, int64_t lda,
                               const double* x, const double* y, const double* z, int64_t col0, int64_t ncols,
                               double l1, double l2, double w, double amp, double* AK, int64_t ldak, void* stream) {
   if (!A || !x || !y || !z || !AK) return GEOBO_E_ARG;

@@ -463,6 +463,38 @@ def gemm_nn(X, Y, C_, alpha=1.0, beta=0.0, x_lower=False, y_lower=False):
     return C_
 
 
+# entry -> (ymode of the core, reduce epilogue); see geobo_gemm_map in include/geobo_hip.h
+_GEMM_ENTRIES = {"ak_fused": (0, 0), "ak_points": (0, 0), "ak_fused_grid": (3, 0), "gemm_nt": (1, 0), "gemm_nt_splitk": (1, 0),
+                 "gemm_nn": (2, 0), "gemm_batched_nt": (1, 0), "gemm_batched_nn": (2, 0), "gemm_batched_xkm": (4, 0),
+                 "posterior_reduce": (2, 1)}
+
+
+def gemm_map(m, n, small_tiles=False, lower_only=False, x_lower=False, y_lower=False, batch=1, entry="gemm_nt", m_valid=0):
+    """The workgroup -> tile map the GEMM core takes for a call of `entry` (a key of _GEMM_ENTRIES) with these public arguments:
+    dict(map, ntiles, nblocks, grid_y, nbi, nbj, tm).  Host arithmetic only (geobo_gemm_map), no GPU needed.  batch: the batch of
+    gemm_batched_* or the splits of gemm_nt_splitk.  posterior_reduce: m, n = shape of AK, x_lower is implied, m_valid as there."""
+    lib = _lib.load()
+    ymode, reduce = _GEMM_ENTRIES[entry]
+    m, n = int(m), int(n)
+    if n % 128 or m % 128:
+        raise ValueError("gemm_map: m and n must be multiples of 128")
+    tri = (1 if lower_only else 0) | (2 if x_lower else 0) | (4 if y_lower else 0)
+    if entry == "posterior_reduce":
+        # 256-row tiles aligned to the END of the valid rows (row_shift of geobo_posterior_reduce)
+        groups = ((m_valid if 0 < m_valid < m else m) + 63) // 64
+        tm, nbi, tri = 256, (groups + 3) // 4, 2
+    elif entry == "gemm_batched_xkm":
+        tm, nbi = 128, m // 128
+    elif m % 256 == 0 and not small_tiles:
+        tm, nbi = 256, m // 256
+    else:
+        tm, nbi = 128, m // 128
+    nbj = n // 128
+    out = (C.c_int * 4)()
+    _lib.check(lib.geobo_gemm_map(ymode, reduce, nbi, nbj, tm, 128, tri, int(batch), out), "geobo_gemm_map")
+    return dict(map=out[0], ntiles=out[1], nblocks=out[2], grid_y=out[3], nbi=nbi, nbj=nbj, tm=tm)
+
+
 def _check_extents(fn, ops, batch):
     """Operand tiles may overhang the valid rows -- by contract into slack of the same allocation: checked before the launch."""
     for T, lead, stride, rows, cols, what in ops:

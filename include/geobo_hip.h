@@ -224,6 +224,19 @@ int geobo_gemm_nt(int64_t m, int64_t n, int64_t k, double alpha, const double* X
 int64_t geobo_tile_order(int nbi, int nbj, int tm, int tn, int lower_only, int x_lower, int y_lower, int* out_host,
                          int64_t capacity);
 
+/* Host-side view of the workgroup -> tile map a launch of the GEMM core takes (pure arithmetic, no device call: the launches
+ * themselves decide through the same function).  Arguments are what the launch sees:
+ *   ymode            0 covariance generator (geobo_ak_fused, geobo_ak_points), 1 NT, 2 NN, 3 lattice table
+ *                    (geobo_ak_fused_grid), 4 NT with X given transposed (GEOBO_GEMM_X_KM);
+ *   reduce_epilogue  != 0 for geobo_posterior_reduce, 0 for every storing entry;
+ *   nbi, nbj         row / column tile counts; tm in {128, 256}, tn = 128 the tile extents;
+ *   tri_flags        1 lower_only | 2 x_lower | 4 y_lower;   batch >= 1 (split-K: the number of splits).
+ * out[0] = map: 0 column-major tiles, 1 one row tile per XCD, 2 4 x 8 supertiles per XCD (triangular X: 1 x 32),
+ *               3 the balanced item order of geobo_tile_order, 32 consecutive (batch, tile) items per XCD;
+ * out[1] = items per batch under map 3 (0 otherwise);  out[2], out[3] = x and y extent of the grid in workgroups.
+ * Used by the tests to pin the map each GEMM case runs under. */
+int geobo_gemm_map(int ymode, int reduce_epilogue, int nbi, int nbj, int tm, int tn, int tri_flags, int batch, int* out);
+
 /* C = X * Y^T with the contraction split into `splits` slices that run concurrently (more, shorter workgroups: fills the
  * chip when m/256 * n/128 is only a few hundred tiles, as in AkA) and are summed in fixed order afterwards (deterministic).
  * ws: splits * m * n doubles.  k % (16 * splits) == 0.  m_valid as in geobo_gemm_nt (rows >= m_valid of C become 0). */

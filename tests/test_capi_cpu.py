@@ -96,6 +96,70 @@ def test_tile_order_visits_every_tile_once(nbi, nbj, tm, tn):
             assert [bj for _, bj in got] == sorted(bj for _, bj in got)
 
 
+def _map_rule(ymode, reduce, nbi, nbj, tm, tn, tri, batch, lower_items):
+    """Plain transcription of the choice in launch() (gemm_f64.hip): (map, items per batch, grid x, grid y)."""
+    mem = ymode in (1, 2, 4)
+    lower, xy = tri & 1, tri & 6
+    xcd_map = 1 if nbi >= 8 else 0
+    if mem and not lower and nbi >= 4 and nbj >= 8:
+        xcd_map = 2
+    ntiles = 0
+    if (mem and not reduce and batch <= 64 and nbi * nbj >= (16 if xy else 64) and nbi * nbj * batch <= 65536 and nbi <= 4096
+            and xy != 6):
+        ntiles = lower_items if lower else nbi * nbj
+        if ntiles > 0:
+            xcd_map = 3
+    if xcd_map == 3:
+        groups = (ntiles * batch + 31) // 32
+        return 3, ntiles, 256 * ((groups + 7) // 8), 1
+    nblocks = nbi * nbj
+    if xcd_map == 1:
+        nblocks = 8 * ((nbi + 7) // 8) * nbj
+    if xcd_map == 2:
+        nst = nbi * ((nbj + 31) // 32) if tri & 2 else ((nbi + 3) // 4) * ((nbj + 7) // 8)
+        nblocks = 256 * ((nst + 7) // 8)
+    return xcd_map, 0, nblocks, batch
+
+
+@pytest.mark.parametrize("ymode", [0, 1, 2, 3, 4])
+def test_gemm_map_matches_the_launch_rule(ymode):
+    """geobo_gemm_map is the function launch() itself calls: map, item count and grid against the rule written out in Python, for
+    every flag combination, both tile heights, both epilogues and batches on either side of the map-3 limit of 64."""
+    from geobo_amd import _lib
+    L = _lib.load()
+    out = (ctypes.c_int * 4)()
+    seen = set()
+    for tm in (128, 256):
+        for nbi in range(1, 41):
+            for nbj in range(1, 41):
+                # tiles with col0 < row0 + tm: row tile bi has its first ceil((bi + 1) tm / 128) column tiles
+                lower_items = sum(min(nbj, -(-(bi + 1) * tm // 128)) for bi in range(nbi))
+                for tri in range(8):
+                    for batch in (1, 3, 64, 65):
+                        for reduce in (0, 1):
+                            assert L.geobo_gemm_map(ymode, reduce, nbi, nbj, tm, 128, tri, batch, out) == 0
+                            want = _map_rule(ymode, reduce, nbi, nbj, tm, 128, tri, batch, lower_items)
+                            assert tuple(out) == want, (ymode, reduce, nbi, nbj, tm, tri, batch)
+                            seen.add(want[0])
+    assert seen == ({0, 1, 2, 3} if ymode in (1, 2, 4) else {0, 1})
+    for bad in ((5, 0, 4, 4, 256, 128, 0, 1), (1, 0, 0, 4, 256, 128, 0, 1), (1, 0, 4, 4, 64, 128, 0, 1), (1, 0, 4, 4, 256, 64, 0, 1),
+                (1, 0, 4, 4, 256, 128, 8, 1), (1, 0, 4, 4, 256, 128, 0, 0)):
+        assert L.geobo_gemm_map(*bad, out) == -1
+
+
+def test_gemm_map_wrapper_picks_the_tile_height():
+    """hip.gemm_map does the tile choice of launch_by_rows: 256-row tiles when m % 256 == 0 and not small_tiles, else 128."""
+    from geobo_amd import hip
+    assert hip.gemm_map(2304, 1024) == dict(map=3, ntiles=72, nblocks=256, grid_y=1, nbi=9, nbj=8, tm=256)
+    assert hip.gemm_map(1280, 1024, small_tiles=True)["tm"] == 128 and hip.gemm_map(1152, 1024)["nbi"] == 9
+    assert hip.gemm_map(2304, 384) == dict(map=1, ntiles=0, nblocks=48, grid_y=1, nbi=9, nbj=3, tm=256)
+    assert hip.gemm_map(1152, 1024, batch=65, entry="gemm_batched_nt")["map"] == 2
+    assert hip.gemm_map(1152, 1024, batch=64, entry="gemm_batched_nt")["ntiles"] == 72
+    r = hip.gemm_map(1280, 1152, entry="posterior_reduce", m_valid=1100)
+    assert (r["map"], r["nbi"], r["nbj"], r["nblocks"]) == (2, 5, 9, 256)
+    assert hip.gemm_map(2304, 256, entry="ak_fused")["map"] == 1 and hip.gemm_map(256, 256, entry="ak_fused_grid")["map"] == 0
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "geobo_amd")
     for dirpath, _, files in os.walk(pkg):

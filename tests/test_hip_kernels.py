@@ -69,6 +69,7 @@ def test_gemm_views_and_triangular_modes(hip):
     ref = 7.0 - P @ P.t()
     low = torch.tril(torch.ones(m, m, device="cuda")).bool()
     assert (C - ref)[low].abs().max().item() < 1e-11
+    assert bool((C[:256, 256:] == 7.0).all())       # 256-row x 128-column tiles: the tiles with col0 >= row0 + 256 are skipped
 
 
 @pytest.mark.parametrize("name", ["exp", "matern32", "sparse"])
