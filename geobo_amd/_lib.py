@@ -86,7 +86,7 @@ SIGNATURES = {
     "geobo_potrf_ws_bytes": (_sz, [_i64]),
     "geobo_potrf_ctx_create": (_int, [C.POINTER(C.c_void_p)]),
     "geobo_potrf_ctx_destroy": (_int, [_dp]),
-    "geobo_potrf_inv": (_int, [_i64, _dp, _i64, _dp, _i64, _dp, _dp, _sz, _dp, _dp]),
+    "geobo_potrf_inv": (_int, [_i64, _dp, _i64, _dp, _i64, _dp, _dp, _sz, _dp, _int, _dp]),
     "geobo_posterior_ws_bytes": (_sz, [_i64, _i64]),
     "geobo_posterior_reduce": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _dp, _f64, _dp, _dp, _i64, _dp, _sz, _dp]),
     "geobo_kinv_dot_ws_bytes": (_sz, [_i64, _int]),

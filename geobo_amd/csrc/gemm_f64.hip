@@ -28,6 +28,7 @@
 #include <stdint.h>
 #include "covfun.h"
 #include "geobo_hip.h"
+#include "lds_optin.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -707,13 +708,7 @@ int launch(GemmArgs& a, hipStream_t st) {
   auto kern = gemm_f64_kernel<WM, WN, YMODE, EPI, KID>;
   // opt-in to > 64 KiB dynamic LDS, once per DEVICE (the attribute lives with the device's code object); idempotent
   static std::atomic<uint64_t> attr_done{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   if (a.m_valid <= 0) a.m_valid = (int64_t)1 << 62;
   if (a.n_valid <= 0) a.n_valid = (int64_t)1 << 62;
   if (a.batch <= 0) a.batch = 1;

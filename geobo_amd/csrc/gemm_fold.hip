@@ -18,6 +18,7 @@
 #include <atomic>
 #include <stdint.h>
 #include "geobo_hip.h"
+#include "lds_optin.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -290,15 +291,8 @@ __global__ void __launch_bounds__(256, 2) gemm_fold_kernel(const FoldArgs a) {
 
 template <int MODE, bool LAM = false>
 int launch_fold(const FoldArgs& a, int64_t batch, hipStream_t st) {
-  static std::atomic<uint64_t> attr_done{0};     // opt-in to > 64 KiB dynamic LDS, once per DEVICE (as in gemm_f64.hip)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fold_kernel<MODE, LAM>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)LDS_BYTES) != hipSuccess)
-      return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  static std::atomic<uint64_t> attr_done{0};     // opt-in to > 64 KiB dynamic LDS, once per DEVICE (lds_optin.h)
+  if (int rc = ensure_lds_attr(attr_done, gemm_fold_kernel<MODE, LAM>, LDS_BYTES)) return rc;
   hipLaunchKernelGGL((gemm_fold_kernel<MODE, LAM>), dim3((unsigned)(a.nbi * a.nbj), (unsigned)batch), dim3(256), LDS_BYTES, st, a);
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }

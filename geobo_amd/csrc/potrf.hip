@@ -3,7 +3,7 @@
 // (inversion.py:105-110).
 //
 // From m = 1024: ONE persistent launch, the tile DAG further down (round 5; round 6: the diagonal block's pivot tile in a row layout
-// without LDS memory, and up to 40 block columns one workgroup walking the latency chain).  Below, and with GEOBO_POTRF=streams, the
+// without LDS memory, and up to 40 block columns one workgroup walking the latency chain).  Below, and with schedule = GEOBO_POTRF_STREAMS, the
 // stream schedule of rounds 2-4 -- right-looking, block size 128:
 //   potf2_inv_kernel  one workgroup factors the 128x128 diagonal block in registers (2-D cyclic over 256 threads),
 //                     carrying the inverse along by forward substitution, and writes L_kk and L_kk^-1 (the latter
@@ -17,9 +17,9 @@
 #include <atomic>
 #include <new>
 #include <stdint.h>
-#include <stdlib.h>
 #include <type_traits>
 #include "geobo_hip.h"
+#include "lds_optin.h"
 
 namespace {
 
@@ -1115,24 +1115,17 @@ size_t dag_ctl_bytes(int64_t nb) {
 
 // one persistent launch (the tile DAG above): counters zeroed on the stream, grid = one workgroup per CU
 int potrf_inv_dag(int64_t m, double* A, int64_t ld, double* Linv, int64_t ldi, int* info, int* ctl, hipStream_t st) {
-  static std::atomic<uint64_t> attr_done{0};   // opt-in to > 64 KiB dynamic LDS, once per DEVICE (idempotent; as in gemm_f64.hip)
+  static std::atomic<uint64_t> attr_done{0}, attr_done_walk{0};   // > 64 KiB dynamic LDS (lds_optin.h): one mask per kernel, both set
+  if (int rc = ensure_lds_attr(attr_done, potrf_dag_kernel<false>, DAG_LDS_BYTES)) return rc;
+  if (int rc = ensure_lds_attr(attr_done_walk, potrf_dag_kernel<true>, DAG_LDS_BYTES)) return rc;
   int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(potrf_dag_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)DAG_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(potrf_dag_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)DAG_LDS_BYTES) != hipSuccess)
-      return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  if (hipGetDevice(&dev) != hipSuccess) return GEOBO_E_LAUNCH;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return GEOBO_E_LAUNCH;
   const int nb = (int)(m / NB);
   if (hipMemsetAsync(ctl, 0, dag_ctl_bytes(nb), st) != hipSuccess) return GEOBO_E_LAUNCH;
   DagArgs a;
   a.A = A; a.ld = ld; a.Linv = Linv; a.ldi = ldi; a.info = info; a.ctl = ctl; a.nb = nb;
   a.xdelay = DAG_XDELAY;
-  if (const char* e = getenv("GEOBO_POTRF_XDELAY")) { const int v = atoi(e); if (v >= 0 && v <= 64) a.xdelay = v; }
   int grid = cus < nb * nb ? cus : nb * nb;
   if (DAG_WALKER && grid >= 2 && nb <= DAG_WALK_NB) hipLaunchKernelGGL(potrf_dag_kernel<true>, dim3(grid), dim3(256), DAG_LDS_BYTES, st, a);
   else hipLaunchKernelGGL(potrf_dag_kernel<false>, dim3(grid), dim3(256), DAG_LDS_BYTES, st, a);
@@ -1175,7 +1168,8 @@ extern "C" int geobo_potrf_ctx_destroy(void* ctx) {
 }
 
 extern "C" int geobo_potrf_inv(int64_t m, double* A, int64_t ld, double* Linv, int64_t ldi, int* info, void* ws,
-                               size_t ws_bytes, void* ctx, void* stream) {
+                               size_t ws_bytes, void* ctx, int schedule, void* stream) {
+  if (schedule != GEOBO_POTRF_AUTO && schedule != GEOBO_POTRF_STREAMS && schedule != GEOBO_POTRF_DAG) return GEOBO_E_ARG;
   if (!A || !Linv || !info || !ws) return GEOBO_E_ARG;
   if (ctx) {   // the fork streams belong to one device: refuse a context made for another one
     int dev = -1;
@@ -1186,10 +1180,8 @@ extern "C" int geobo_potrf_inv(int64_t m, double* A, int64_t ld, double* Linv, i
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(info, 0, sizeof(int), st) != hipSuccess) return GEOBO_E_LAUNCH;
   // From m = 1024: the persistent tile DAG (one launch; every tile of Linv is written by it, no memset).  Below -- the tiny grids of
-  // optimize_gp's search, see the note at blocked_potf2 -- and with GEOBO_POTRF=streams: the stream schedule that follows.
-  bool dag = m >= 1024;
-  if (const char* e = getenv("GEOBO_POTRF")) dag = e[0] == 'd';
-  if (dag) {
+  // optimize_gp's search, see the note at blocked_potf2 -- and with schedule = GEOBO_POTRF_STREAMS: the stream schedule that follows.
+  if (schedule == GEOBO_POTRF_AUTO ? m >= 1024 : schedule == GEOBO_POTRF_DAG) {
     const int64_t nbd = m / NB;
     return potrf_inv_dag(m, A, ld, Linv, ldi, info, reinterpret_cast<int*>((char*)ws + (size_t)tree_doubles((int)nbd) * sizeof(double)), st);
   }

@@ -36,6 +36,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "geobo_hip.h"
+#include "lds_optin.h"
 
 namespace {
 
@@ -384,13 +385,7 @@ int launch_full(const std::conditional_t<WIN, SYWinArgs, SYArgs>& g, hipStream_t
   static_assert(lds <= 163840, "LDS");
   auto kern = spectral_y_kernel<NY, NIN, NOUT, FULL, WIN>;
   static std::atomic<uint64_t> attr_done{0};       // per-device "large-LDS attribute set" bits (include/geobo_hip.h, conventions)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   const int64_t nbx = (g.C + 63) / 64;
   // a wave keeps its 16 modes for R / gy rows.  Two property blocks / two terms take more than 256 registers: one 4-wave workgroup per
   // CU, one round; a single block fits 256 -- two workgroups per CU, 0.850 -> 0.808 ms (profiles/r06_spectral_y_ab.txt)
@@ -894,12 +889,7 @@ int launch_split(const SY3Args& g, hipStream_t st) {
   if constexpr (PIPE) kern = reinterpret_cast<const void*>(spectral_y_pipe_kernel<NY, NIN, NOUT, ACC>);
   else kern = reinterpret_cast<const void*>(spectral_y_split_kernel<NY, NIN, NOUT, ACC>);
   static std::atomic<uint64_t> attr_done{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   const int64_t nbx = g.C / 16;
   int64_t gy = 1;                                   // one workgroup per CU: a workgroup keeps its 16 modes for R / gy rows
   while (nbx * gy < 512 && gy < g.R) ++gy;

@@ -17,6 +17,7 @@
 #include <atomic>
 #include <stdint.h>
 #include "geobo_hip.h"
+#include "lds_optin.h"
 
 namespace {
 
@@ -271,13 +272,7 @@ int launch2(const Toeplitz2Args& g, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * 2 * NY * 64 * sizeof(double);
   auto kern = toeplitz_y2_kernel<NY>;
   static std::atomic<uint64_t> attr_done{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   int64_t gy = g.R < 2 ? g.R : 2;      // one workgroup per CU: 256 column blocks x 2 at 64^3 = two rounds of the chip
   while ((g.C / 64) * gy < 512 && gy < g.R) ++gy;
   hipLaunchKernelGGL(kern, dim3((unsigned)(g.C / 64), (unsigned)gy), dim3(512), lds, st, g);
@@ -436,13 +431,7 @@ int launch2s(const Toeplitz2sArgs& g, hipStream_t st) {
   static_assert(lds <= 163840, "LDS");
   auto kern = toeplitz_y2s_kernel<NY>;
   static std::atomic<uint64_t> attr_done{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   int64_t gy = g.R < 2 ? g.R : 2;      // one workgroup per CU: 256 column blocks x 2 at 64^3 = two rounds of the chip
   while ((g.C / 64) * gy < 512 && gy < g.R) ++gy;
   hipLaunchKernelGGL(kern, dim3((unsigned)(g.C / 64), (unsigned)gy), dim3(512), lds, st, g);
@@ -588,13 +577,7 @@ int launch_win(const ToeplitzWinArgs& g, hipStream_t st) {
   constexpr size_t lds = (size_t)2 * NY * 64 * sizeof(double);
   auto kern = toeplitz_y_win_kernel<NY, OC, ACC>;
   static std::atomic<uint64_t> attr_done{0};      // per-device "large-LDS attribute set" bits (include/geobo_hip.h, conventions)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if (!((attr_done.load(std::memory_order_acquire) >> dev) & 1)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GEOBO_E_LAUNCH;
-    attr_done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  }
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   const int nchunks = (g.y1 - g.y0 + OC - 1) / OC;
   if (g.nprop == 3 && nchunks >= 2) {
     // three blocks are six waves with ONE chunk each; as 2 + 1 blocks every launch has eight waves and two / four chunks per

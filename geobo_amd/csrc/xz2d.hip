@@ -21,18 +21,9 @@
 #include <atomic>
 #include <stdint.h>
 #include "geobo_hip.h"
+#include "lds_optin.h"
 
 namespace {
-
-// opt-in to > 64 KiB dynamic LDS, once per DEVICE (not per process: a second device needs its own call); idempotent
-int ensure_lds_attr(std::atomic<uint64_t>& done, const void* kern, size_t lds) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if ((done.load(std::memory_order_acquire) >> dev) & 1) return GEOBO_OK;
-  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GEOBO_E_LAUNCH;
-  done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  return GEOBO_OK;
-}
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -232,7 +223,7 @@ int launch(const XZArgs& g, hipStream_t st) {
   using K = XZCfg<IN_X, IN_Z, OUT_X, OUT_Z>;
   auto kern = xz2d_kernel<IN_X, IN_Z, OUT_X, OUT_Z>;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), K::LDS)) return rc;
+  if (int rc = ensure_lds_attr(attr_done, kern, K::LDS)) return rc;
   int64_t nwg = g.nplanes < 1024 ? g.nplanes : 1024;  // persistent: 4 workgroups per CU over the launch, >= 8 planes each at 64^3
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * K::NW), K::LDS, st, g);
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
@@ -557,7 +548,7 @@ extern "C" int geobo_xcorr_reduce(int nx, int nz, int64_t rows, int planes, cons
   constexpr int NW = 8;
   auto kern = xcorr_kernel<NX, NZ, PX, NW>;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), lds)) return rc;
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   const int64_t nwg = g.nplanes < 1024 ? g.nplanes : 1024;
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * NW), lds, (hipStream_t)stream, g);
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;

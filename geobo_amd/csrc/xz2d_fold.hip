@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "geobo_hip.h"
+#include "lds_optin.h"
 
 // Cache policy of the spectrum streams (A/B, round 6): the forward transform's 8 MB / row of output and the inverse transform's input are
 // touched once per launch.  XZF_NT_ST: non-temporal stores of the forward output; XZF_NT_LD: aux = nt on the inverse's LDS-DMA loads.
@@ -71,15 +72,6 @@ struct FoldArgs {
 };
 
 constexpr int vmcnt_imm(int v) { return (v & 15) | (7 << 4) | (15 << 8) | ((v >> 4) << 14); }
-
-int ensure_lds_attr(std::atomic<uint64_t>& done, const void* kern, size_t lds) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GEOBO_E_LAUNCH;
-  if ((done.load(std::memory_order_acquire) >> dev) & 1) return GEOBO_OK;
-  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GEOBO_E_LAUNCH;
-  done.fetch_or((uint64_t)1 << dev, std::memory_order_release);
-  return GEOBO_OK;
-}
 
 // row i of a chunk in LDS <- row rowperm(i) of the chunk in memory: D register reg = i >> 2 of lane group q = i & 3
 __device__ __forceinline__ int rowperm(int i) { return 8 * (i >> 3) + 2 * (i & 3) + ((i >> 2) & 1); }
@@ -1272,7 +1264,7 @@ int launch_fwd(const FoldArgs& g, hipStream_t st) {
   using K = FwdCfg<N, 4>;
   auto kern = xz_fold_fwd_kernel<N, QUAD>;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), K::LDS)) return rc;
+  if (int rc = ensure_lds_attr(attr_done, kern, K::LDS)) return rc;
   const int64_t nwg = g.nplanes < 2048 ? g.nplanes : 2048;   // persistent, two workgroups per CU resident
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), K::LDS, st, g);
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
@@ -1284,7 +1276,7 @@ int launch_inv(const FoldArgs& g, hipStream_t st) {
   constexpr bool RED = MODE == 1;
   auto kern = xz_fold_inv_kernel<N, MODE, QUAD>;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), K::LDS)) return rc;
+  if (int rc = ensure_lds_attr(attr_done, kern, K::LDS)) return rc;
   int64_t nwg = g.nplanes < 2048 ? g.nplanes : 2048;
   if (RED) nwg = nwg / g.ppr * g.ppr;                          // every workgroup keeps one y: grid = whole rows of planes
   if (nwg <= 0) return GEOBO_E_ARG;
@@ -1296,7 +1288,7 @@ int launch_conv_fwd(const FoldArgs& g, hipStream_t st) {
   using K = ConvFwdCfg<64, XZF_CF_RING>;
   auto kern = xz_conv_fwd_kernel<64, XZF_CF_RING>;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), K::LDS)) return rc;
+  if (int rc = ensure_lds_attr(attr_done, kern, K::LDS)) return rc;
   // persistent, plane-strided, as launch_fwd / launch_inv (512 and 1024 workgroups, and a start-up stagger of every other one,
   // measured the same to 1 %)
   const int64_t nwg = g.nplanes < 2048 ? g.nplanes : 2048;
@@ -1324,7 +1316,7 @@ extern "C" int geobo_xcorr_reduce_fold(int n, int64_t rows, int planes, const do
   constexpr size_t lds = (size_t)4 * 16 * N * 8 + (size_t)4 * 16 * 16 * 16 + 2 * 4 * (2 * N) * 8;
   auto kern = xcorr_fold4_kernel<N>;
   static std::atomic<uint64_t> attr_done{0};
-  if (int rc = ensure_lds_attr(attr_done, reinterpret_cast<const void*>(kern), lds)) return rc;
+  if (int rc = ensure_lds_attr(attr_done, kern, lds)) return rc;
   if (planes > 2048) return GEOBO_E_UNSUPPORTED;
   const int64_t rper = 2048 / planes;                       // persistent: every workgroup keeps one y-mode (its eigenvalues in registers)
   const int64_t nwg = (int64_t)planes * (rows < rper ? rows : rper);

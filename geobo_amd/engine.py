@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import geometry, hip
-from .plan import COLUMN_FORM_MAX_BYTES, plan_route
+from .plan import COLUMN_FORM_MAX_BYTES, engine_options, plan_route
 from .columnform import ColumnExchangeMixin
 from .rowform import RowFormMixin
 from .operators import StreamedOperator
@@ -191,8 +191,11 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self.method = method
         # every shape / rank-count / precision decision of a step comes from ONE pure function (plan.py, CPU-tested table); the
         # GEOBO_* switches are overrides into it.  What a step then actually ran is recorded in self.step_route.
+        # The options the planner does not own (plan.ENGINE_OPTIONS) are resolved from the same mapping, here and nowhere else.
+        env = os.environ
         self.route = plan_route(self.nx, self.ny, self.nz, world=world, rank=rank, assembly=assembly, operators=operators, method=method,
-                                env=os.environ)
+                                env=env)
+        self.options = engine_options(env)
         self.use_spectral = self.route.spectral
         if method == "spectral" and not self.use_spectral:
             raise ValueError("spectral method needs grid extents % 16 == 0 and column shards on y-slab boundaries")
@@ -205,14 +208,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self._lattice_plan = None
         self._gram, self._lam, self._edgeV = None, {}, {}
         self._lamW, self._edgeVt = {}, {}     # transposed lattice application: permuted eigen-data, boundary-slab spectra
-        # Mirrored magnetic block of AkA ("point mirror"): GEOBO_AKA_MIRROR=0 switches it off -- resolved HERE,
-        # once per engine, not in plan.SWITCHES (the planner's pinned route table counts its switches).  aka_mirror[func]: what the last
+        # Mirrored magnetic block of AkA ("point mirror"): GEOBO_AKA_MIRROR=0 switches it off.  aka_mirror[func]: what the last
         # operator build measured and what the last step did with it -- dict(deviation, bound, symmetric, taken); _mirror: (operator, symmetric)
-        self.aka_mirror_on = os.environ.get("GEOBO_AKA_MIRROR", "1") != "0"
+        self.aka_mirror_on = self.options.aka_mirror
         self.aka_mirror, self._mirror, self._mirror_meas = {}, {}, None
         # Rows of L^-1 A enter the posterior's covariance product as spectra, Z is never stored (transposed._posterior_zpath; DESIGN.md
-        # section 2 item 4): GEOBO_Z_SPECTRUM=0 restores the stored rows.  Resolved here like GEOBO_AKA_MIRROR, for the same reason
-        self.z_spectrum_on = os.environ.get("GEOBO_Z_SPECTRUM", "1") != "0"
+        # section 2 item 4): GEOBO_Z_SPECTRUM=0 restores the stored rows
+        self.z_spectrum_on = self.options.z_spectrum
         # Row form (plan.Route.family "rows", rowform.py): statically possible; whether a step takes it is decided when the operators
         # are built (lattice survey, even stencils).  Column form from 4 ranks: row-sharded transforms + one all-to-all of A K block
         # columns per operator (with 2 ranks the exchange would move a quarter of A K over ONE xGMI link, more than the forward passes
@@ -235,8 +237,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         # (own: torch.distributed.new_group is a collective over the DEFAULT group -- every rank must build its engine at the same
         # point; the communicator is cached per rank tuple and shared by all engines of the process.)
         self._xgroup = group
-        self.async_exchange = os.environ.get("GEOBO_ASYNC_EXCHANGE", "1") != "0"
-        if (self.exchange and os.environ.get("GEOBO_EXCHANGE_COMM", "shared") == "own" and self.async_exchange
+        self.async_exchange = self.options.async_exchange
+        if (self.exchange and self.options.exchange_comm == "own" and self.async_exchange
                 and not isinstance(group, EmulatedGroup) and torch.distributed.is_available() and torch.distributed.is_initialized()):
             ranks = torch.distributed.get_process_group_ranks(group) if group is not None else list(range(torch.distributed.get_world_size()))
             if len(ranks) == world:
@@ -246,7 +248,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self._potrf_ctx = None
         # one-rank runs issue no collective; bench.py --gpus 1 --check and the RCCL test set this so that the row form's all-gather,
         # all-reduce and agreement go through the backend with one rank (sharding._live)
-        self.force_collectives = os.environ.get("GEOBO_FORCE_COLLECTIVES", "0") == "1"
+        self.force_collectives = self.options.force_collectives
         self.kernel_events = None  # set to [] to record (name, flops, start, stop) HIP events per fused launch
         self.aka_hook = None       # callable(AkA) run between the assembly of AkA and its factorisation (emulation tool only)
 
@@ -941,9 +943,10 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
 
     @_on_device
     def posterior(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp=1.0,
-                  props=(0, 1, 2), calclogl=True, want_mean_var=True, keep_K=False):
+                  props=(0, 1, 2), calclogl=True, want_mean_var=True, keep_K=False, potrf_schedule=None):
         """Posterior mean / variance / log-likelihood.  `lengths` must already carry the create_cov mutation.
         Returns dict(mu (3N, NaN for skipped property blocks), var, logl, info).
+        potrf_schedule: the `schedule` of hip.potrf_inv for this step (None: the engine's resolved option, self.options.potrf).
         keep_K (internal, logl_grad): keep a copy of the assembled K without its diagonal (workspace "K_signal") before the
         in-place factorisation."""
         props = tuple(props)
@@ -973,7 +976,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             self._potrf_ctx = hip.PotrfContext()       # fork streams of the L^-1 build: per engine, on this engine's device
         Linv, info = self._timed("potrf_inv", 2.0 * M_pad ** 3 / 3.0, lambda: hip.potrf_inv(
             AkA, self._workspace("Linv", (M_pad, M_pad)), self._workspace("potrf_ws", (hip.potrf_ws_doubles(M_pad),)),
-            ctx=self._potrf_ctx), alg=(2 * self.Ms + len(sel)) ** 3 * 2.0 / 3.0)  # AkA now holds L
+            ctx=self._potrf_ctx, schedule=potrf_schedule or self.options.potrf), alg=(2 * self.Ms + len(sel)) ** 3 * 2.0 / 3.0)  # AkA now holds L
         L = AkA
         self._finish_exchange()
         u, stats = hip.trmv_stats(Linv, y, L)
@@ -1082,7 +1085,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         return self._assemble_AkA(step, self._assemble_AK(step, A_g, A_m), A_g, A_m)
 
     @_on_device
-    def logl_grad(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, directions):
+    def logl_grad(self, A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp, directions,
+                  potrf_schedule=None):
         """Exact gradient of f = (u.u + log det K) / 2 (calc_logl without the N log 2 pi term), K = amp sum_ij W_ij B_ij + D:
             df/dtheta = <S, dK/dtheta> / 2,   S = K^-1 - alpha alpha^T,   alpha = L^-T u,   K^-1 = L^-T L^-1 (never stored).
         One posterior() step (likelihood only) keeps K's signal part; G_0 = that part, plus the unit-weight blocks amp (B_ab + B_ba) of
@@ -1091,7 +1095,8 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         sums of <S, G_t> per pair of row segments, from which
             d_amp = sum over the non-zero-weight pairs / amp,  d_w = pair (a, b) / w (or the unit block's sum where w = 0),
             d_dir[t] = all pairs of G_t,
-        each halved.  Returns dict(uu, logdet, d_amp, d_w (3,), d_dir (len(directions),)).  One rank, fp64 assembly."""
+        each halved.  Returns dict(uu, logdet, d_amp, d_w (3,), d_dir (len(directions),)).  One rank, fp64 assembly.
+        potrf_schedule: as in posterior()."""
         if self.world > 1:
             raise ValueError("logl_grad runs on one rank (world = %d): the multi-rank gradient is not implemented" % self.world)
         if self.f32:
@@ -1101,7 +1106,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             raise ValueError("at most three length directions per evaluation")
         props = (0, 1, 2)
         r = self.posterior(A_g, A_m, sel, y_g, y_m, y_d, lengths, crossweights, kernelfunc, gp_sigma, gp_amp=gp_amp, props=props,
-                           calclogl=True, want_mean_var=False, keep_K=True)
+                           calclogl=True, want_mean_var=False, keep_K=True, potrf_schedule=potrf_schedule)
         W = weight_matrix(crossweights)
         Linv, u = self.last["Linv"], self.last["u"]
         M_pad = Linv.shape[0]

@@ -838,9 +838,15 @@ class PotrfContext:
             pass
 
 
-def potrf_inv(A, Linv=None, ws=None, ctx=None):
+POTRF_SCHEDULES = {"auto": 0, "streams": 1, "dag": 2}      # GEOBO_POTRF_AUTO / _STREAMS / _DAG of include/geobo_hip.h
+
+
+def potrf_inv(A, Linv=None, ws=None, ctx=None, schedule="auto"):
     """In-place lower Cholesky of A (m x m, m % 128 == 0); returns (Linv, info_tensor).  Linv / ws may be caller-owned;
-    ctx: PotrfContext (concurrent L^-1 subtrees) or None (serial on the current stream)."""
+    ctx: PotrfContext (concurrent L^-1 subtrees) or None (serial on the current stream).  schedule: "auto" (the tile DAG from
+    m = 1024, the stream schedule below), "streams" or "dag" (that one at any m)."""
+    if schedule not in POTRF_SCHEDULES:
+        raise ValueError("potrf_inv: schedule must be one of %s, not %r" % (", ".join(map(repr, POTRF_SCHEDULES)), schedule))
     lib = require_gpu()
     ld = _rowmajor(A, "A")
     m = A.shape[0]
@@ -851,7 +857,7 @@ def potrf_inv(A, Linv=None, ws=None, ctx=None):
     if ws is None or ws.numel() * 8 < nbytes:
         ws = torch.empty(max(nbytes // 8, 1), dtype=F64, device=A.device)
     _lib.check(lib.geobo_potrf_inv(m, _p(A), ld, _p(Linv), Linv.stride(0), _p(info), _p(ws), nbytes,
-                                   ctx.handle if ctx is not None else None, _stream()), "geobo_potrf_inv")
+                                   ctx.handle if ctx is not None else None, POTRF_SCHEDULES[schedule], _stream()), "geobo_potrf_inv")
     return Linv, info
 
 

@@ -139,10 +139,10 @@ class Inversion:
         args = (A_g, A_m, self._sel, self.Fs3[:ng], self.Fs3[ng:ng + nm], self.Fs3[ng + nm:], [float(v) for v in lengths],
                 self.coeffm if coeffm is None else coeffm, self.settings.kernelfunc, self.gp_sigma)
         if directions is None:
-            step = lambda: self.engine.posterior(*args, gp_amp=gp_amp, props=self.props, calclogl=calclogl,
-                                                 want_mean_var=want_mean_var)
+            step = lambda **kw: self.engine.posterior(*args, gp_amp=gp_amp, props=self.props, calclogl=calclogl,
+                                                      want_mean_var=want_mean_var, **kw)
         else:
-            step = lambda: self.engine.logl_grad(*args, gp_amp, directions)
+            step = lambda **kw: self.engine.logl_grad(*args, gp_amp, directions, **kw)
         try:
             r = step()
             self._step_params = _hyper_key(gp_amp, lengths, self.coeffm if coeffm is None else coeffm)
@@ -150,20 +150,11 @@ class Inversion:
         except FactorisationTimeout:
             # (round-5 advisory) the tile DAG's bounded spins can trip on a device shared with other processes: once more, on the
             # stream schedule of rounds 2-4 (no inter-workgroup hand-offs), instead of returning an undefined factor
-            import os
             import warnings
             warnings.warn("geobo_potrf_inv: tile-DAG hand-off timed out (info = -7); repeating the step on the stream schedule", RuntimeWarning)
-            before = os.environ.get("GEOBO_POTRF")
-            os.environ["GEOBO_POTRF"] = "streams"
-            try:
-                r = step()
-                self._step_params = _hyper_key(gp_amp, lengths, self.coeffm if coeffm is None else coeffm)
-                return r
-            finally:
-                if before is None:
-                    os.environ.pop("GEOBO_POTRF", None)
-                else:
-                    os.environ["GEOBO_POTRF"] = before
+            r = step(potrf_schedule="streams")
+            self._step_params = _hyper_key(gp_amp, lengths, self.coeffm if coeffm is None else coeffm)
+            return r
 
     # ---- inversion.py:77-122 ----------------------------------------------------------------------------------------
     def predict3(self, calclogl=False, full_cov=False):

@@ -17,7 +17,7 @@ Families (DESIGN.md sections 2 and 7):
              the lattice Gram, row exchange (all-to-all) from 4 ranks.  What runs for surveys off the lattice, the dense method, padded
              shapes and small grids without fused kernels.
 Reference call sites all of these replace: inversion.py:92-117 (predict3), kernels.py:158-195 (create_cov)."""
-from dataclasses import asdict, dataclass
+from dataclasses import asdict, dataclass, make_dataclass
 
 PAD_M, PAD_N = 256, 128
 XZ2D_SHAPES = ((48, 64), (64, 64), (64, 32))      # fused (x, z) transform instances (hip.XZ2D_SHAPES)
@@ -47,7 +47,7 @@ ROWS_MIN_VOXELS_FUSED = 1 << 17                   # with fused / four-plane (x, 
 # Every behaviour switch of a step, in ONE table: option -> the environment override that turns it off ("0").  They are resolved ONCE
 # (switches(); a product built on its own resolves the process environment the same way) into the kernel forms of stage_forms(): the spectral
 # product, the lattice Gram and the transposed posterior decide nothing.  The environment is also read for plan_route's family overrides
-# (GEOBO_ROWS, GEOBO_POSTERIOR, GEOBO_SPECTRAL_EXCHANGE) and the row form's batch size (GEOBO_ROW_CHUNK, rowform.py: a test knob).  All are
+# (GEOBO_ROWS, GEOBO_POSTERIOR, GEOBO_SPECTRAL_EXCHANGE) and for the engine's own options (ENGINE_OPTIONS below).  All are
 # A/B and fallback-coverage switches: the default of every option is "on", every "off" path a complete, tested form of the same arithmetic.
 SWITCHES = {"fused_xz": "GEOBO_SPECTRAL_FUSED_XZ",   # fused (x, z) transform kernels (else two batched passes)
             "fold": "GEOBO_XZ_FOLD",                 # radix-2 / radix-4 transform kernels (else the plain products)
@@ -66,6 +66,26 @@ def switches(env=None):
     """{option: bool} from an environment-like mapping (None: every option on)."""
     env = {} if env is None else env
     return {k: env.get(v, "1") != "0" for k, v in SWITCHES.items()}
+
+
+# The options of an engine that the planner does NOT own (they change no route and no kernel form, so they stay out of SWITCHES and of
+# the pinned route table): field -> (environment variable, default, parser of the variable's text).  Resolved ONCE per engine by
+# engine_options(), from the same mapping that plan_route gets; nothing else in the package reads them.
+_on = lambda v: v != "0"
+ENGINE_OPTIONS = {"aka_mirror": ("GEOBO_AKA_MIRROR", True, _on),               # magnetic block of AkA: one half computed, the other mirrored
+                  "z_spectrum": ("GEOBO_Z_SPECTRUM", True, _on),               # rows of L^-1 A enter the posterior as spectra (else stored rows)
+                  "async_exchange": ("GEOBO_ASYNC_EXCHANGE", True, _on),       # row exchange overlapped with compute (else blocking)
+                  "exchange_comm": ("GEOBO_EXCHANGE_COMM", "shared", str),     # "own": a second communicator for the row exchange
+                  "force_collectives": ("GEOBO_FORCE_COLLECTIVES", False, lambda v: v == "1"),   # one-rank runs go through the backend
+                  "row_chunk": ("GEOBO_ROW_CHUNK", 0, int),                    # rows per batch of the row form (0: from the memory budget; tests)
+                  "potrf": ("GEOBO_POTRF", "auto", lambda v: "dag" if v[:1] == "d" else "streams")}   # schedule of hip.potrf_inv
+EngineOptions = make_dataclass("EngineOptions", [(k, type(d)) for k, (_, d, _p) in ENGINE_OPTIONS.items()], frozen=True)
+
+
+def engine_options(env=None):
+    """EngineOptions from an environment-like mapping (None: every default)."""
+    env = {} if env is None else env
+    return EngineOptions(**{k: parse(env[var]) if var in env else default for k, (var, default, parse) in ENGINE_OPTIONS.items()})
 
 
 def half_integer(n):

@@ -19,8 +19,6 @@ Chunking bounds the footprint by the scratch budget instead of by the cube: 128^
 ~50 GB per rank where the column form needed a 104 GB A K shard.  With one chunk (64^3 from 2 ranks) the launches are those of
 round 3's resident form, bit for bit.  Covariance tables are rounded through fp32 in the fp32-assembly mode (engine._cov_table);
 everything else is fp64."""
-import os
-
 import torch
 
 from . import hip
@@ -36,7 +34,7 @@ class RowFormMixin:
         """Rows per chunk: `nblocks` row blocks of N doubles each inside the scratch budget, whole transform batches."""
         sp = self._spectral
         budget = ROW_SCRATCH_BYTES
-        ck = int(os.environ.get("GEOBO_ROW_CHUNK", "0")) or max(1, budget // (nblocks * self.N * 8))      # (GEOBO_ROW_CHUNK: tests)
+        ck = self.options.row_chunk or max(1, budget // (nblocks * self.N * 8))      # (GEOBO_ROW_CHUNK, plan.engine_options: tests)
         return max(sp.R, ck // sp.R * sp.R)
 
     def _rows_product(self, func, g0, n, lams, outs):

@@ -13,9 +13,10 @@
  *   - functions are stream-ordered, never allocate, never synchronise, never throw; the return value
  *     is 0 on success or a negative GEOBO_E_* code (argument validation / launch failure);
  *   - process-global state: ONE exception to "none" -- kernels that need more than 64 KiB of dynamic LDS record, in a
- *     per-kernel atomic bit mask indexed by device (`attr_done` in gemm_f64.hip, xz2d.hip, xz2d_fold.hip), that
+ *     per-kernel atomic bit mask indexed by device (`attr_done`, set in ONE place: ensure_lds_attr of csrc/lds_optin.h), that
  *     hipFuncSetAttribute(MaxDynamicSharedMemorySize) has been issued for that device.  The flag is idempotent, lock free,
- *     never cleared and carries no data: concurrent first calls at worst issue the attribute twice;
+ *     never cleared and carries no data: concurrent first calls at worst issue the attribute twice.  The library reads no
+ *     environment variable: every choice is an argument;
  *   - PADDING CONTRACT: matrix operands are allocated with their dimensions rounded up to
  *     GEOBO_PAD_M (rows of M-like dims) / GEOBO_PAD_N (voxel-like dims) and the padding is ZERO
  *     (identity on the diagonal of matrices that get factorised).  Kernels then run without edge
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GEOBO_VERSION 212 /* 201: flag word of geobo_gemm_nt, (64, 32) instance of geobo_xz2d, workspace layout of geobo_potrf_inv; 202: geobo_ymul, geobo_xz2d_fold_lattice; 203: geobo_sumsq_accum, geobo_lamdot_z, geobo_toeplitz_y2t, geobo_xz2d_fold_quad; 204: geobo_toeplitz_y3_add; 205: workspace layout of geobo_potrf_inv (one T buffer per tree node); 206: geobo_potrf_inv as one persistent tile-DAG launch from m = 1024 (workspace: + counters); 207: geobo_gemm_fold; 208: geobo_gemm_fold_lamdot; 209: geobo_toeplitz_y2s; 210: geobo_xz2d_fold* dense planes take the quarter-period group order of the basis (radix 4); 211: geobo_ymul_fold; 212: geobo_spectral_y, geobo_spectral_y2s, geobo_spectral_y_basis, geobo_spectral_y3, geobo_spectral_y3t, geobo_spectral_axis, geobo_rowgemv */
+#define GEOBO_VERSION 213 /* 201: flag word of geobo_gemm_nt, (64, 32) instance of geobo_xz2d, workspace layout of geobo_potrf_inv; 202: geobo_ymul, geobo_xz2d_fold_lattice; 203: geobo_sumsq_accum, geobo_lamdot_z, geobo_toeplitz_y2t, geobo_xz2d_fold_quad; 204: geobo_toeplitz_y3_add; 205: workspace layout of geobo_potrf_inv (one T buffer per tree node); 206: geobo_potrf_inv as one persistent tile-DAG launch from m = 1024 (workspace: + counters); 207: geobo_gemm_fold; 208: geobo_gemm_fold_lamdot; 209: geobo_toeplitz_y2s; 210: geobo_xz2d_fold* dense planes take the quarter-period group order of the basis (radix 4); 211: geobo_ymul_fold; 212: geobo_spectral_y, geobo_spectral_y2s, geobo_spectral_y_basis, geobo_spectral_y3, geobo_spectral_y3t, geobo_spectral_axis, geobo_rowgemv; 213: geobo_potrf_inv takes its schedule as an argument (GEOBO_POTRF_*) instead of reading the environment */
 
 /* Additive since 212, version unchanged: covariance ids 7-15 (partial derivatives in the lengths, accepted by geobo_k_block,
  * geobo_k_block_f32, geobo_k_eval, geobo_cov_table and geobo_ak_fused), geobo_kinv_dot and geobo_kinv_dot_ws_bytes.  No existing
@@ -527,7 +528,7 @@ int geobo_spectral_axis(int inverse, int n, int64_t C, int64_t plane_in, int64_t
  * = -7 reports a scheduler time-out (never seen; the result is then undefined).  ctx is not used by that form.  Up to 40 block columns
  * (m <= 5120, round 6) ONE workgroup walks the latency chain -- diagonal tile, tile under it, update of the next diagonal tile -- with
  * the other workgroups parking the partial sums it needs; larger matrices keep every link a task of its own.  Below m = 1024, or
- * with GEOBO_POTRF=streams in the environment, the stream schedule of rounds 2-4 runs:
+ * with schedule = GEOBO_POTRF_STREAMS, the stream schedule of rounds 2-4 runs:
  * ctx: fork context or NULL.  With a context (three internal streams, ordered after / before `stream` by events) the
  * trailing update of every step runs one step behind on the first stream (look-ahead), and the L^-1 tree -- dozens of small
  * merges -- is built under the factorisation: every node's two GEMMs are queued on the second stream as soon as the columns of L
@@ -535,12 +536,15 @@ int geobo_spectral_axis(int inverse, int n, int64_t C, int64_t plane_in, int64_t
  * A context is made ONCE at set-up time (geobo_potrf_ctx_create: the only entry points of this library that
  * create runtime objects, never called from a launch path), belongs to the device that was current then, and serves one
  * factorisation at a time: concurrent factorisations (other streams, other threads, other devices) each bring their own.
- * The library keeps no process-global streams, events, caches or locks. */
+ * The library keeps no process-global streams, events, caches or locks.
+ * schedule: GEOBO_POTRF_AUTO is the rule above (the tile DAG from m = 1024, the stream schedule below); GEOBO_POTRF_STREAMS and
+ * GEOBO_POTRF_DAG force one of them at any m.  Any other value: GEOBO_E_ARG, checked before anything else. */
+enum { GEOBO_POTRF_AUTO = 0, GEOBO_POTRF_STREAMS = 1, GEOBO_POTRF_DAG = 2 };
 size_t geobo_potrf_ws_bytes(int64_t m);
 int geobo_potrf_ctx_create(void** ctx);
 int geobo_potrf_ctx_destroy(void* ctx);
 int geobo_potrf_inv(int64_t m, double* A, int64_t ld, double* Linv, int64_t ldi, int* info, void* ws,
-                    size_t ws_bytes, void* ctx, void* stream);
+                    size_t ws_bytes, void* ctx, int schedule, void* stream);
 
 /* Row dot products  out[r] = sum_(c < n) X[r, c] * v[c]  of a row-major matrix (n even, ld even, X and v 16-byte aligned): a forward
  * operator applied to a model, data = A rho (simcube.py:147-150 -- the synthetic surveys of bench.py and of the tests; np.dot there).

@@ -15,7 +15,7 @@ BOXES = [(1, 1, 1), (2, 2, 2), (4, 3, 4), GRID]               # (by, bx, bz); (4
 def test_block_cov_validates_without_gpu():
     from geobo_amd import _lib
     L = _lib.load()
-    assert L.geobo_version() == 212
+    assert L.geobo_version() == 213
     p = 16                                                     # (never dereferenced: every call below fails its checks first)
     ws = L.geobo_block_cov_ws_bytes
     N = 5 * 6 * 7

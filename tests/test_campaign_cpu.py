@@ -72,7 +72,7 @@ def test_path_sets_unique_padding_and_leaving():
 def test_set_entry_points_validate_without_gpu():
     from geobo_amd import _lib
     L = _lib.load()
-    assert L.geobo_version() == 212
+    assert L.geobo_version() == 213
     p = 16                                                 # (never dereferenced: every call below fails its checks first)
     assert L.geobo_set_gram(4, 16, None, 8, p, 64, 64, 0, p, None) == -1
     assert L.geobo_set_gram(4, 129, p, 8, p, 64, 64, 0, p, None) == -1

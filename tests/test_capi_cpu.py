@@ -43,7 +43,7 @@ def test_host_side_helpers(lib):
     lib.geobo_pad_n.argtypes = [ctypes.c_int64]
     lib.geobo_potrf_ws_bytes.restype = ctypes.c_size_t
     lib.geobo_potrf_ws_bytes.argtypes = [ctypes.c_int64]
-    assert lib.geobo_version() == 212
+    assert lib.geobo_version() == 213
     assert lib.geobo_pad_m(8242) == 8448 and lib.geobo_pad_m(256) == 256 and lib.geobo_pad_m(1) == 256
     assert lib.geobo_pad_n(480) == 512 and lib.geobo_pad_n(262144) == 262144
     # one T buffer per node [lo, mid, hi) of the L^-1 tree, (hi - mid) x (mid - lo) blocks of 128 x 128; split on even block counts
@@ -68,7 +68,29 @@ def test_argument_validation_without_gpu(lib):
     L = _lib.load()
     assert L.geobo_gemm_nt(256, 128, 16, 1.0, None, 16, None, 16, 0.0, None, 128, 0, 0, None) == -1
     assert L.geobo_ak_fused(1, None, 256, 256, 256, None, None, None, 0, 128, 1., 1., 1., 1., None, 128, None) == -1
-    assert L.geobo_potrf_inv(100, None, 100, None, 100, None, None, 0, None, None) == -1
+    assert L.geobo_potrf_inv(100, None, 100, None, 100, None, None, 0, None, 0, None) == -1
+    # an unknown schedule is refused FIRST: with pointers that must not be looked at (nothing here is device memory) and no device
+    for dummy in (0x1000, 0x7fff0000):
+        assert L.geobo_potrf_inv(256, dummy, 256, dummy, 256, dummy, dummy, 1 << 30, None, 7, None) == -1
+        assert L.geobo_potrf_inv(256, dummy, 256, dummy, 256, dummy, dummy, 1 << 30, None, -1, None) == -1
+    hdr = open(os.path.join(ROOT, "include", "geobo_hip.h")).read()
+    assert re.search(r"GEOBO_POTRF_AUTO = 0, GEOBO_POTRF_STREAMS = 1, GEOBO_POTRF_DAG = 2\b", hdr)
+    from geobo_amd import hip
+    assert hip.POTRF_SCHEDULES == {"auto": 0, "streams": 1, "dag": 2}
+    with pytest.raises(ValueError):
+        hip.potrf_inv(None, schedule="stream")
+
+
+def test_the_library_reads_no_environment(lib):
+    """Every choice reaches the C library as an argument: it imports no getenv (a minimal hipcc-built shared object imports none either,
+    so the runtime's own start-up code does not hide one), and no source under csrc names it."""
+    import subprocess
+    from geobo_amd.build import CSRC, LIB
+    syms = subprocess.run(["nm", "-D", "--undefined-only", LIB], capture_output=True, text=True, check=True).stdout.split()
+    assert any(s.startswith("hipLaunchKernel") for s in syms)                   # (the listing is what it should be: the runtime's entry points are in it)
+    assert not [s for s in syms if "getenv" in s]
+    for f in sorted(os.listdir(CSRC)):
+        assert "getenv" not in open(os.path.join(CSRC, f)).read(), f
 
 
 @pytest.mark.parametrize("nbi,nbj,tm,tn", [(33, 32, 256, 128), (33, 66, 256, 128), (66, 66, 128, 128), (5, 3, 128, 128), (4, 64, 256, 128),

@@ -133,7 +133,7 @@ def test_long_double_reference_solves():
 def test_crossval_entry_points_validate_without_gpu():
     from geobo_amd import _lib
     L = _lib.load()
-    assert L.geobo_version() == 212
+    assert L.geobo_version() == 213
     p = 16                                                 # (never dereferenced: every call below fails its checks first)
     ws = lambda m: L.geobo_kinv_diag_ws_bytes(m)
     assert L.geobo_kinv_diag(256, None, 256, p, p, p, p, ws(256), None) == -1

@@ -127,16 +127,12 @@ def test_set_loo_by_value(k):
 # ---- 3. the two device paths agree -----------------------------------------------------------------------------------------------
 # (below m = 1024 the default schedule is the stream schedule: the 1024 case is the one that runs the tile DAG)
 @pytest.mark.parametrize("schedule,m", [("default", 512), ("streams", 512), ("default", 1024)])
-def test_singleton_and_set_routes_agree(schedule, m, monkeypatch):
+def test_singleton_and_set_routes_agree(schedule, m):
     from geobo_amd import hip
-    if schedule == "streams":
-        monkeypatch.setenv("GEOBO_POTRF", "streams")
-    else:
-        monkeypatch.delenv("GEOBO_POTRF", raising=False)
     rng = np.random.default_rng(5)
     X = rng.standard_normal((m, 2 * m))
     A = _dev(X @ X.T / (2 * m) + 0.05 * np.eye(m))
-    Linv, info = hip.potrf_inv(A, ctx=hip.PotrfContext())
+    Linv, info = hip.potrf_inv(A, ctx=hip.PotrfContext(), schedule="auto" if schedule == "default" else schedule)
     assert int(info.cpu()[0]) == 0
     assert float(torch.triu(Linv, 1).abs().max()) == 0.0                   # set_gram over columns of L^-1 relies on it
     u = Linv @ _dev(rng.standard_normal(m))

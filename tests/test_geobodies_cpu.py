@@ -25,14 +25,14 @@ def _i32(*v):
 def test_symbols_and_signatures():
     from geobo_amd import _lib, build
     L = _lib.load()
-    assert L.geobo_version() == 212
+    assert L.geobo_version() == 213
     assert "geobodies.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "geobodies.hip"))
     header = open(os.path.join(ROOT, "include", "geobo_hip.h")).read()
     for name in ("geobo_bodies", "geobo_bodies_ws_bytes"):
         assert name + "(" in header
         assert name in _lib.SIGNATURES
         assert getattr(L, name).argtypes == _lib.SIGNATURES[name][1]
-    assert "#define GEOBO_VERSION 212 " in header
+    assert "#define GEOBO_VERSION 213 " in header
     assert len(_lib.SIGNATURES["geobo_bodies"][1]) == 27 and len(_lib.SIGNATURES["geobo_bodies_ws_bytes"][1]) == 5
 
 

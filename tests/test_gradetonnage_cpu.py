@@ -16,7 +16,7 @@ def _dbl(*v):
 def test_symbols_and_signatures():
     from geobo_amd import _lib, build
     L = _lib.load()
-    assert L.geobo_version() == 212
+    assert L.geobo_version() == 213
     assert "gradetonnage.hip" in build.SOURCES
     for name in ("geobo_box_means", "geobo_cutoff_stats", "geobo_cutoff_stats_ws_bytes"):
         assert name in _lib.SIGNATURES

@@ -205,17 +205,22 @@ def test_ak_fused_grid_matches_coordinate_path(hip, name, cross, dims):
     assert np.array_equal(sh.cpu().numpy(), got.cpu().numpy()[:, Np - 128:])
 
 
-@pytest.mark.parametrize("fork", [False, True])
-# 10, 18, 23, 33, 66 blocks of 128: L^-1 spines of depth 1, 1, 2, 3, 3 (odd and even splits) built under the factorisation;
-# 2, 4 blocks: the plain serial tree
-@pytest.mark.parametrize("m", [256, 512, 1280, 2304, 2944, 4224, 8448])
-def test_potrf_inv_matches_torch(hip, m, fork):
+# The (m, fork) grid under schedule "auto" (the stream schedule below m = 1024, the persistent tile DAG from there; fork is not used by the
+# DAG): 2, 4 blocks of 128 are the plain serial tree.  "streams" at 10 and 23 blocks: the time-out's fallback above the threshold, with the
+# L^-1 tree's spine of depth 1 and 2 built under the factorisation (with a fork context: on its own stream).  "dag" below the threshold.
+POTRF_CASES = ([pytest.param(m, fork, "auto", id="%d-%s" % (m, fork)) for m in (256, 512, 1280, 2304, 2944, 4224, 8448) for fork in (False, True)]
+               + [pytest.param(m, fork, "streams", id="%d-%s-streams" % (m, fork)) for m in (1280, 2944) for fork in (False, True)]
+               + [pytest.param(512, False, "dag", id="512-False-dag")])
+
+
+@pytest.mark.parametrize("m,fork,schedule", POTRF_CASES)
+def test_potrf_inv_matches_torch(hip, m, fork, schedule):
     B = _rand((m, m), 20)
     S = B @ B.t() / m + 0.05 * torch.eye(m, dtype=torch.float64, device="cuda")
     L = S.clone()
-    # (the result buffer arrives poisoned: from m = 1024 the persistent tile-DAG launch writes every tile of Linv itself, zeros included)
+    # (the result buffer arrives poisoned: the persistent tile-DAG launch writes every tile of Linv itself, zeros included)
     Linv, info = hip.potrf_inv(L, Linv=torch.full((m, m), float("nan"), dtype=torch.float64, device="cuda"),
-                               ctx=hip.PotrfContext() if fork else None)
+                               ctx=hip.PotrfContext() if fork else None, schedule=schedule)
     assert int(info.item()) == 0
     Lref = torch.linalg.cholesky(S)
     assert (torch.tril(L) - Lref).abs().max().item() < 1e-12

@@ -260,6 +260,57 @@ def test_route_table():
     assert "spectral/rows" in plan_route(64, 64, 64, world=8).describe()
 
 
+# variable -> (field of plan.engine_options, [(text of the variable, resolved value), ...]); the first entry of DEFAULTS is the empty environment
+ENGINE_OPTION_DEFAULTS = dict(aka_mirror=True, z_spectrum=True, async_exchange=True, exchange_comm="shared", force_collectives=False,
+                              row_chunk=0, potrf="auto")
+ENGINE_OPTION_TABLE = {"GEOBO_AKA_MIRROR": ("aka_mirror", [("0", False), ("1", True)]),
+                       "GEOBO_Z_SPECTRUM": ("z_spectrum", [("0", False), ("1", True)]),
+                       "GEOBO_ASYNC_EXCHANGE": ("async_exchange", [("0", False), ("1", True)]),
+                       "GEOBO_EXCHANGE_COMM": ("exchange_comm", [("own", "own"), ("shared", "shared")]),
+                       "GEOBO_FORCE_COLLECTIVES": ("force_collectives", [("1", True), ("0", False)]),
+                       "GEOBO_ROW_CHUNK": ("row_chunk", [("64", 64), ("256", 256), ("0", 0)]),
+                       # the rule the library had while it read the variable itself: unset auto, a leading "d" the DAG, anything else the streams
+                       "GEOBO_POTRF": ("potrf", [("streams", "streams"), ("dag", "dag"), ("d", "dag"), ("stream", "streams"), ("auto", "streams"),
+                                                 ("", "streams")])}
+
+
+def test_engine_options_table():
+    """plan.engine_options: the empty environment gives the defaults; each variable set singly changes exactly its own field; the record is
+    frozen, and the planner's own variables do not reach it."""
+    import dataclasses
+    from geobo_amd import plan
+    assert dataclasses.asdict(plan.engine_options({})) == ENGINE_OPTION_DEFAULTS == dataclasses.asdict(plan.engine_options(None))
+    assert sorted(v for v, _, _ in plan.ENGINE_OPTIONS.values()) == sorted(ENGINE_OPTION_TABLE)
+    assert not set(ENGINE_OPTION_TABLE) & set(plan.SWITCHES.values())
+    for var, (field, cases) in ENGINE_OPTION_TABLE.items():
+        for text, want in cases:
+            got = dataclasses.asdict(plan.engine_options({var: text}))
+            assert got == dict(ENGINE_OPTION_DEFAULTS, **{field: want}), (var, text)
+            assert type(got[field]) is type(ENGINE_OPTION_DEFAULTS[field])
+    assert plan.engine_options({"GEOBO_ROW_CHUNK": "64"}).row_chunk == 64
+    assert [plan.engine_options(e).potrf for e in ({}, {"GEOBO_POTRF": "streams"}, {"GEOBO_POTRF": "dag"})] == ["auto", "streams", "dag"]
+    assert plan.engine_options({"GEOBO_ROWS": "1", "GEOBO_XZ_FOLD": "0", "GEOBO_HIP_LIB": "x"}) == plan.engine_options({})
+    with pytest.raises(dataclasses.FrozenInstanceError):
+        plan.engine_options({}).potrf = "dag"
+
+
+def test_the_package_reads_the_environment_in_three_places():
+    """`environ` occurs in the package's Python sources only where the library path is read (_lib.py), at the engine's one hand-off to the
+    planner and to plan.engine_options, and as the default of a SpectralProduct built on its own.  Nothing writes it."""
+    import glob
+    import os
+    import re
+    from conftest import ROOT
+    hits = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "geobo_amd", "*.py"))):
+        for no, line in enumerate(open(path).read().split("\n"), 1):
+            hits += [(os.path.basename(path), line.strip())] * len(re.findall(r"\benviron\b", line))     # (the word: not "environment")
+    assert [f for f, _ in hits] == ["_lib.py", "engine.py", "spectral.py"], hits
+    want = {"_lib.py": 'LIB_PATH = os.environ.get("GEOBO_HIP_LIB") or', "engine.py": "env = os.environ", "spectral.py": "plan.switches(os.environ) if opts is None else opts"}
+    for f, line in hits:
+        assert want[f] in line, (f, line)
+
+
 def test_planner_and_kernel_wrappers_share_one_instance_table():
     """Round-4 advisory: plan.py carried its own copies of the kernel-instance tables.  They are now defined once (plan.py) and
     re-exported by hip.py / LatticeGram; this pins that."""

@@ -29,7 +29,7 @@ def _header_args(name):
 def test_symbols_and_signatures():
     from geobo_amd import _lib, build
     L = _lib.load()
-    assert L.geobo_version() == 212
+    assert L.geobo_version() == 213
     assert "intercepts.hip" in build.SOURCES
     host = {"t", "lo"}                                         # host arrays travel as POINTER(c_double), device pointers as void*
     for name in ("geobo_trace_stats", "geobo_trace_stats_ws_bytes"):

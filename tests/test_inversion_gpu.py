@@ -1363,3 +1363,60 @@ def test_auto_operators_with_an_inclined_field_match_resident_operators():
         torch.cuda.empty_cache()
     for a, b in zip(out["auto"], out["resident"]):
         assert np.isnan(b).all() if np.isnan(a).all() else normwise(a, b) <= 1e-11
+
+
+def test_dag_timeout_repeats_the_step_on_the_stream_schedule_by_argument(monkeypatch):
+    """The retry after a tile-DAG time-out (info = -7) hands the stream schedule to the step as an argument: nothing writes the process
+    environment.  32 x 16 x 16 with 20 drill rows: M_pad = 1280, so the default schedule is the tile DAG.
+      (a) a step as it is (the DAG);
+      (b) hip.potrf_inv wrapped: the first call runs normally, then its status word is overwritten with -7 (a status word only: no
+          fault, no real time-out) -- the step must warn, repeat with schedule="streams", leave os.environ alone, and give the bits of
+      (c) an engine built under GEOBO_POTRF=streams (plan.engine_options);
+    (a) and (b) differ only in the factor's summation order: 1e-10 normwise."""
+    import bench
+    from geobo_amd import hip
+    from geobo_amd.inversion import Inversion
+    monkeypatch.delenv("GEOBO_POTRF", raising=False)
+    s = settings_for(32, 16, 16, kernelfunc="matern32")
+    lengths = np.array([200.0, 202.0, 204.0])
+
+    def run(inv, inputs):
+        grav, mag, loc, drill0 = inputs
+        inv.gp_length = lengths.copy()
+        cubes = inv.cubing(grav, mag, drill0[drill0 != 0], loc, drill0)
+        return cubes, inv.logl
+
+    a = Inversion(settings=s)
+    inputs = bench.synthetic_inputs(a, 20)
+    cubes_a, logl_a = run(a, inputs)
+    assert a.engine.options.potrf == "auto" and a.engine.last["Linv"].shape[0] == 1280
+
+    calls, real = [], hip.potrf_inv
+
+    def potrf_inv(A, *args, **kw):
+        calls.append(kw.get("schedule", "auto"))
+        Linv, info = real(A, *args, **kw)
+        if len(calls) == 1:
+            info.fill_(-7)
+        return Linv, info
+    b = Inversion(settings=s)
+    env_before = dict(os.environ)
+    monkeypatch.setattr(hip, "potrf_inv", potrf_inv)
+    with pytest.warns(RuntimeWarning, match=r"tile-DAG hand-off timed out \(info = -7\); repeating the step on the stream schedule"):
+        cubes_b, logl_b = run(b, inputs)
+    monkeypatch.setattr(hip, "potrf_inv", real)
+    assert calls == ["auto", "streams"]
+    assert dict(os.environ) == env_before and b.engine.options.potrf == "auto"
+
+    monkeypatch.setenv("GEOBO_POTRF", "streams")
+    c = Inversion(settings=s)
+    cubes_c, logl_c = run(c, inputs)
+    assert c.engine.options.potrf == "streams"
+
+    assert logl_b == logl_c
+    for cb, cc, ca in zip(cubes_b, cubes_c, cubes_a):
+        assert np.array_equal(cb, cc)
+        print("DAG against stream schedule, normwise: %.2e" % normwise(cb, ca))
+        assert normwise(cb, ca) <= 1e-10
+    print("logl: DAG %.12e streams %.12e" % (logl_a, logl_b))
+    assert abs(logl_b - logl_a) <= 1e-10 * abs(logl_a)

@@ -1,4 +1,4 @@
-"""geobo_potrf_inv, persistent tile-DAG form against torch and against the stream schedule (GEOBO_POTRF=streams):
+"""geobo_potrf_inv, persistent tile-DAG form against torch and against the stream schedule (schedule="streams"):
     python tools/check_potrf_dag.py [m ...]"""
 import os
 import sys
@@ -19,7 +19,6 @@ for m in sizes:
     ws = torch.empty(hip.potrf_ws_doubles(m), dtype=torch.float64, device="cuda")
     ctx = hip.PotrfContext()
     for mode in ("dag", "streams"):
-        os.environ["GEOBO_POTRF"] = mode
         ts = []
         for rep in range(4):
             L = S.clone()
@@ -27,7 +26,7 @@ for m in sizes:
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            _, info = hip.potrf_inv(L, Linv, ws, ctx=ctx)
+            _, info = hip.potrf_inv(L, Linv, ws, ctx=ctx, schedule=mode)
             e1.record()
             torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1))
@@ -37,8 +36,7 @@ for m in sizes:
         print("m=%5d %-7s info=%d  |L-Lref|=%.2e  |Linv L - I|=%.2e  upper(Linv)=%.1e  ms=%s" % (
             m, mode, int(info.item()), eL, eI, up, " ".join("%.2f" % t for t in ts)), flush=True)
     # run to run: bit-identical
-    os.environ["GEOBO_POTRF"] = "dag"
-    L1 = S.clone(); X1 = torch.empty_like(S); hip.potrf_inv(L1, X1, ws)
-    L2 = S.clone(); X2 = torch.empty_like(S); hip.potrf_inv(L2, X2, ws)
+    L1 = S.clone(); X1 = torch.empty_like(S); hip.potrf_inv(L1, X1, ws, schedule="dag")
+    L2 = S.clone(); X2 = torch.empty_like(S); hip.potrf_inv(L2, X2, ws, schedule="dag")
     torch.cuda.synchronize()
     print("        bit-identical repeat:", torch.equal(torch.tril(L1), torch.tril(L2)) and torch.equal(X1, X2), flush=True)

@@ -1,5 +1,5 @@
 """geobo_potrf_inv at the 64^3 headline size (M_pad = 8448), with and without the fork context (look-ahead + concurrent L^-1
-subtrees); for rocprofv3 --kernel-trace timelines:  python tools/run_potrf_once.py [m] [ctx|noctx]"""
+subtrees); for rocprofv3 --kernel-trace timelines:  python tools/run_potrf_once.py [m] [ctx|noctx] [auto|streams|dag]"""
 import os
 import sys
 import time
@@ -10,6 +10,7 @@ from geobo_amd import hip
 
 m = int(sys.argv[1]) if len(sys.argv) > 1 else 8448
 modes = [sys.argv[2]] if len(sys.argv) > 2 else ["noctx", "ctx"]
+schedule = sys.argv[3] if len(sys.argv) > 3 else "auto"
 g = torch.Generator().manual_seed(0)
 B = torch.rand((m, 512), generator=g, dtype=torch.float64).cuda()
 S = B @ B.t() / 512 + 0.5 * torch.eye(m, dtype=torch.float64, device="cuda")
@@ -22,7 +23,7 @@ for mode in modes:
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
-        e0.record(); hip.potrf_inv(L, Linv, ws, ctx=ctx); e1.record()
+        e0.record(); hip.potrf_inv(L, Linv, ws, ctx=ctx, schedule=schedule); e1.record()
         t_host = time.perf_counter() - t0
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1)
