@@ -506,6 +506,142 @@ __global__ void __launch_bounds__(256, 2) ymul_kernel(YMulArgs g) {
   if (prev_tile >= 0) store(prev, prev_tile);
 }
 
+// ---- lattice Gram from x-analysed rows: y step + eigenvalue scaling + channel sum (geobo_gram_yz) -------------------------------
+// s[r][ky][o] = sum_z lam[ky][o][z] * sum_y G[ky][y] GX[r][y][o][z]: the rows arrive with the x analysis already done (the inverse
+// transform of the A K product emits GX, geobo_xz2d_fold_inv_gx), so the y spectrum -- 2 ny x 2 nx x nz doubles per row -- is never
+// written.  The y step is ymul_kernel<true>: G in registers as folded A fragments, the (ny x 64) tile GX[r][:, o, :] (ny runs of
+// 512 bytes) through the two-stage LDS ring by LDS-DMA.  A workgroup keeps ONE x-mode o and walks the rows (as xcorr_fold4_kernel
+// keeps one y-mode): its 2 ny x 64 eigenvalues stay in registers, 32 per lane, laid out like the D tiles.  Epilogue per row: D * lam,
+// summed over z in the registers (4 column tiles) and across the 16 lanes of a group (a halving exchange: 8 shuffles for the lane's 8
+// values), one store per even lane.  Tile rows >= ny are zeroed once and never staged (ny < 64: the k-steps meet zeros).
+struct GramYZArgs {
+  const double* gx; int64_t gx_row, gx_plane;   // tile (r, o): row y at gx + r*gx_row + y*gx_plane + o*64
+  const double* G; int64_t ldg;                 // (2 ny) x ny, pair-interleaved
+  const double* lam;                            // [2 ny][128][64]
+  double* s; int64_t s_row, s_plane;            // s + r*s_row + ky*s_plane + o
+  int64_t R; int ny, rstep;                     // grid = 128 * rstep workgroups
+};
+
+__global__ void __launch_bounds__(256, 2) gram_yz_kernel(GramYZArgs g) {
+  constexpr int NY = 64, CB = 64, TILE = NY * CB, PX = 128;
+  __shared__ __attribute__((aligned(16))) double xs[2][TILE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, q = lane >> 4;
+  // Workgroups that follow each other by 8 share a memory-side cache slice on a multi-die device: they take the 16 x-modes of one
+  // 128-byte line of s and the same row, so that their 8-byte results meet there.
+  const int bid = blockIdx.x, o = (bid & 7) * 16 + ((bid >> 3) & 15);
+  int64_t r = bid >> 7;
+  if (r >= g.R) return;
+  const int ny = g.ny;
+  double a[2][8];                                          // a[0][t] = Fe[b = 16 w + lr][j = 4 t + q] = G[2 b][2 j], a[1][t] = Fo[b][j] = G[2 b][2 j + 1]
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const int b = 16 * w + lr, y = 2 * (4 * t + q) + mt;
+      a[mt][t] = (b < ny && y < ny) ? g.G[(int64_t)(2 * b) * g.ldg + y] : 0.0;
+    }
+  double lam[2][4][4];                                     // [mt][nt][r4]: ky = 2 (16 w + q + 4 r4) + mt, z = 16 nt + lr
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int r4 = 0; r4 < 4; ++r4) {
+        const int ky = 2 * (16 * w + q + 4 * r4) + mt;
+        lam[mt][nt][r4] = ky < 2 * ny ? g.lam[((int64_t)ky * PX + o) * CB + 16 * nt + lr] : 0.0;
+      }
+  if (ny < NY) {
+    for (int i = tid; i < 2 * TILE; i += 256) (&xs[0][0])[i] = 0.0;
+  }
+  __syncthreads();
+  const int dma_h = lane >> 5;
+  const int64_t dma_lane = (int64_t)dma_h * g.gx_plane + ((lane & 31) ^ (((2 * w + dma_h) & 3) << 3)) * 2;
+  auto stage = [&](int64_t r_, int b) {
+    const double* src = g.gx + r_ * g.gx_row + (int64_t)o * CB + dma_lane;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int pr = w + 4 * i;                              // row pair
+      if (2 * pr < ny)
+        __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + (int64_t)(2 * pr) * g.gx_plane), (lds_ptr_t)(&xs[b][2 * pr * CB]), 16, 0, 0);
+    }
+  };
+  stage(r, 0);
+  int b = 0;
+  const bool h8 = lr & 8, h4 = lr & 4, h2 = lr & 2;
+  const int kyo = 2 * (16 * w + q + 4 * (lr >> 2)) + ((lr >> 1) & 1);   // the y-mode an even lane stores
+  for (; r < g.R; r += g.rstep) {
+    __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));              // this tile has landed (and the previous row's results are out)
+    __builtin_amdgcn_s_barrier();                          // ... for every wave; every wave is done reading the other stage
+    const int64_t nxt = r + g.rstep;
+    if (nxt < g.R) stage(nxt, b ^ 1);
+    v4d acc[2][4];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = (v4d){0., 0., 0., 0.};
+    // (the k-steps of ymul_kernel<true>: even rows y = 8 t + 2 q feed E, odd rows y + 1 feed O)
+    unsigned xe[4], xo[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      xe[nt] = (unsigned)(uintptr_t)(lds_ptr_t)&xs[b][(2 * q) * CB + 16 * (nt ^ ((2 * q) & 3)) + lr];
+      xo[nt] = (unsigned)(uintptr_t)(lds_ptr_t)&xs[b][(2 * q + 1) * CB + 16 * (nt ^ ((2 * q + 1) & 3)) + lr];
+    }
+    double be[2][4], bo[2][4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      asm volatile("ds_read_b64 %0, %1" : "=v"(be[0][nt]) : "v"(xe[nt]));
+      asm volatile("ds_read_b64 %0, %1" : "=v"(bo[0][nt]) : "v"(xo[nt]));
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      if (t + 1 < 8) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(be[(t + 1) & 1][nt]) : "v"(xe[nt]), "n"(8 * (t + 1) * CB * 8));
+          asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(bo[(t + 1) & 1][nt]) : "v"(xo[nt]), "n"(8 * (t + 1) * CB * 8));
+        }
+        asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(be[t & 1][0]), "+v"(be[t & 1][1]), "+v"(be[t & 1][2]), "+v"(be[t & 1][3]),
+                     "+v"(bo[t & 1][0]), "+v"(bo[t & 1][1]), "+v"(bo[t & 1][2]), "+v"(bo[t & 1][3]));
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(be[t & 1][0]), "+v"(be[t & 1][1]), "+v"(be[t & 1][2]), "+v"(be[t & 1][3]),
+                     "+v"(bo[t & 1][0]), "+v"(bo[t & 1][1]), "+v"(bo[t & 1][2]), "+v"(bo[t & 1][3]));
+      }
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        acc[0][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0][t], be[t & 1][nt], acc[0][nt], 0, 0, 0);
+        acc[1][nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1][t], bo[t & 1][nt], acc[1][nt], 0, 0, 0);
+      }
+    }
+    // ---- D * lam summed over z: the lane's 4 column tiles, then the 16 lanes of the group --------------------------------------
+    double v[8];                                           // [2 r4 + mt]
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4)
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        double sum = 0.0;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+          const double d = mt ? acc[0][nt][r4] - acc[1][nt][r4] : acc[0][nt][r4] + acc[1][nt][r4];   // rows 2 b (E + O) and 2 b + 1 (E - O)
+          sum = __builtin_fma(d, lam[mt][nt][r4], sum);
+        }
+        v[2 * r4 + mt] = sum;
+      }
+    // halving exchange: after the step over lane bit k a lane keeps the half of its values that bit selects, summed with its
+    // partner's -- lane lr ends with the total of value (lr >> 1)
+    double k4[4], k2[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) k4[i] = (h8 ? v[4 + i] : v[i]) + __shfl_xor(h8 ? v[i] : v[4 + i], 8);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) k2[i] = (h4 ? k4[2 + i] : k4[i]) + __shfl_xor(h4 ? k4[i] : k4[2 + i], 4);
+    double k1 = (h2 ? k2[1] : k2[0]) + __shfl_xor(h2 ? k2[0] : k2[1], 2);
+    k1 += __shfl_xor(k1, 1);
+    if (!(lr & 1) && kyo < 2 * ny) g.s[r * g.s_row + (int64_t)kyo * g.s_plane + o] = k1;
+    b ^= 1;
+  }
+}
+
 }  // namespace
 
 extern "C" int geobo_xz2d(int inverse, int nx, int nz, int64_t rows, int planes_per_row, const double* in, int64_t in_row,
@@ -565,6 +701,22 @@ extern "C" int geobo_ymul(int m, int k, int64_t C, int64_t rows, const double* G
   g.ntiles = rows * (C / 64);
   const int64_t nwg = g.ntiles < 512 ? g.ntiles : 512;   // persistent: two workgroups per CU, 32 tiles each at 64^3
   hipLaunchKernelGGL(ymul_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, g);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
+
+extern "C" int geobo_gram_yz(int n, int ny, int64_t rows, const double* gx, int64_t gx_row, int64_t gx_plane, const double* G, int64_t ldg,
+                             const double* lam, double* s, int64_t s_row, int64_t s_plane, void* stream) {
+  if (!gx || !G || !lam || !s) return GEOBO_E_ARG;
+  if (((uintptr_t)gx & 15) || ((uintptr_t)G & 7) || ((uintptr_t)lam & 7) || ((uintptr_t)s & 7)) return GEOBO_E_ARG;
+  if ((gx_row & 1) || (gx_plane & 1) || gx_plane < 2 * (int64_t)n * n || gx_row < 0 || s_plane < 2 * n || s_row < 0) return GEOBO_E_ARG;
+  if (ny < 2 || (ny & 1) || ldg < ny) return GEOBO_E_ARG;
+  if (n != 64 || ny > 64) return GEOBO_E_UNSUPPORTED;
+  if (rows <= 0) return GEOBO_OK;
+  GramYZArgs g;
+  g.gx = gx; g.gx_row = gx_row; g.gx_plane = gx_plane; g.G = G; g.ldg = ldg; g.lam = lam; g.s = s; g.s_row = s_row; g.s_plane = s_plane;
+  g.R = rows; g.ny = ny;
+  g.rstep = rows < 4 ? (int)rows : 4;                      // persistent: 512 workgroups, two per CU, every one keeps its x-mode
+  hipLaunchKernelGGL(gram_yz_kernel, dim3((unsigned)(128 * g.rstep)), dim3(256), 0, (hipStream_t)stream, g);
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }
 

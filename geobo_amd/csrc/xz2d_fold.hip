@@ -55,12 +55,20 @@ struct FoldArgs {
   // forward only, lattice survey (geobo_xz2d_fold_lattice): the planes of an operator row are windows of the stencil table --
   // row r, plane y at in + row_off[r] + y*in_plane, except the first and the last plane of a row (the 1e6-padded boundary slabs),
   // which come from edge + r*edge_row (+ one plane for the last one).  row_off == nullptr: dense rows as above.
-  const int64_t* row_off; const double* edge; int64_t edge_row;
+  const int64_t* row_off; const double* edge;
+  union { int64_t edge_row; int64_t gx_all; };   // (gx_all: MODE 3 of the inverse, below)
   // inverse with the sum-of-squares reduction (geobo_xz2d_fold_inv_ss): rows r >= r2_first are the SUM of two spectra, plane (r, y)
   // of the second one at in2 + (r - r2_first)*in2_row + y*in_plane (both contractions are linear: the first step accumulates over
   // the terms, the second runs once); nothing is stored per plane -- every workgroup keeps sum_r X_r[y]^2 for its fixed y in
   // registers and adds it to ss + (slot*ppr + y)*n*n at the end (slot = blockIdx.x / ppr; the grid is a multiple of ppr)
-  const double* in2; int64_t in2_row, r2_first; double* ss;
+  // inverse with the lattice Gram's x analysis (geobo_xz2d_fold_inv_gx, MODE 3): every interior plane (r, y), 0 < y < ppr - 1, is also
+  // carried through the forward x step and stored as GX[o][z] (2N x N) at gx + r*gx_row + y*gx_plane; gx_all == 0: only the two
+  // boundary planes of a row are stored to out.  (The mode reads none of the reduction form's arguments and takes their places: the
+  // argument block of the other instances keeps its size.)
+  const double* in2;
+  union { int64_t in2_row; int64_t gx_row; };
+  union { int64_t r2_first; int64_t gx_plane; };
+  union { double* ss; double* gx; };
   // QUAD form (geobo_xz2d_fold_quad; n = 32 planes on the n = 64 kernels): a 2N x 2N / N x N "plane" of the kernel is a 2 x 2 arrangement
   // of four consecutive planes of half the extent -- [[y, y+1], [y+2, y+3]] -- and the folded matrices are those of diag(G32, G32):
   // four independent transforms per kernel plane (half of the MFMAs meet zero blocks; the passes are HBM bound either way).  Memory
@@ -445,9 +453,16 @@ struct InvCfg {
 // W = Lambda[iz] * lhat_r never exists in memory).  MUL stages its chunks through registers instead of LDS-DMA: every thread loads
 // its 4 x 16 bytes of both factors two chunks ahead (two register sets), multiplies and writes the ring slot itself; the chunk
 // barrier waits for those LDS writes only.
+// MODE 3 (GX; dense planes): mode 0, and every interior plane of a row also goes through the lattice Gram's forward x step before it
+// leaves the registers (geobo_xz2d_fold_inv_gx).  After the inverse phase lane (lr, q) of wave w holds X[16 r' + 4 q + rho][4 lr + w]
+// in xe[rho >> 1][rho & 1][r']: register r' of class rho IS the B fragment (k = q <-> class input j = 4 r' + q, column z = 4 lr + w) of
+// the radix-4 analysis of xcorr_fold4_kernel, so no hand-off is needed.  The A fragments are the class image the inverse already
+// keeps in LDS, read transposed ([om = lr][j = 4 r' + q] instead of [j = lr][om]): 16 reads and 32 MFMAs per wave and plane, then the
+// eight outputs of every frequency (the butterflies of xcorr_fold4_kernel: the same spectral positions o) are stored as GX[o][z].
 template <int N, int MODE, bool QUAD>
 __global__ void __launch_bounds__(256, 2) xz_fold_inv_kernel(FoldArgs g) {
-  constexpr bool RED = MODE == 1, MUL = MODE == 2;
+  constexpr bool RED = MODE == 1, MUL = MODE == 2, GX = MODE == 3;
+  static_assert(!(GX && QUAD), "the x analysis rides on the radix-4 form");
   const int in_rowB = QUAD ? g.in_rowB : 2 * N * 8, in_halfB = QUAD ? g.in_halfB : N * 8, in_botB = QUAD ? g.in_botB : 0;
   const int out_halfB = QUAD ? g.out_halfB : N * 4, out_botB = QUAD ? g.out_botB : 0;
   // Radix 4 (dense planes) along BOTH axes: along z wave w owns the outputs z = 4 (lane column) + w; along x (the spectral rows of a
@@ -757,8 +772,60 @@ __global__ void __launch_bounds__(256, 2) xz_fold_inv_kernel(FoldArgs g) {
         sso[m] += od * od;
       }
     } else {
+      bool ak_store = true, drained = false;
+      if constexpr (GX) {
+        const int y = (int)(p % g.ppr);
+        const bool interior = y != 0 && y != g.ppr - 1;       // (uniform: the boundary planes do not enter the interior Gram)
+        ak_store = g.gx_all || !interior;
+        if (interior) {
+          // ---- forward x step on the plane in the registers: cosine-row sums C_rho (gc) and sine-row sums S_rho (gs) per class ------
+          v4d gc[4], gs[4];
+#pragma unroll
+          for (int rho = 0; rho < 4; ++rho) gc[rho] = gs[rho] = (v4d){0., 0., 0., 0.};
+          // image element (rho, j, om) sits in slot om ^ j of row j: A[i = om = lr][k = q <-> j = 4 c + q] at
+          // (fxT ^ (c << 6)) + c * 1024 + rho * 4096
+          unsigned fxT = (unsigned)(uintptr_t)(lds_ptr_t)mxf + q * 256 + ((lr ^ q) << 4);
+          asm volatile("" : "+v"(fxT));
+          static_for<0, 4>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            v2d f[4];
+            const unsigned fa4 = fxT ^ (unsigned)(c << 6);
+#pragma unroll
+            for (int rho = 0; rho < 4; ++rho)
+              asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f[rho]) : "v"(fa4), "n"(c * 1024 + rho * 4096));
+            static_for<0, 4>([&](auto rr) {
+              constexpr int rho = decltype(rr)::value;
+              asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f[rho]) : "n"(3 - rho));
+              gc[rho] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].x, xe[rho >> 1][rho & 1][c], gc[rho], 0, 0, 0);
+              gs[rho] = __builtin_amdgcn_mfma_f64_16x16x4f64(f[rho].y, xe[rho >> 1][rho & 1][c], gs[rho], 0, 0, 0);
+            });
+          });
+          __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));           // (as below: the next plane's first chunks, ahead of this plane's stores)
+          drained = true;
+          // register r of a lane = frequency om = q + 4 r at z = 4 lr + w: its eight sums give the spectral positions 8 om .. 8 om + 7
+          double* const gp = g.gx + (p / g.ppr) * g.gx_row + y * g.gx_plane + (int64_t)(8 * q) * N + 4 * lr + w;
+          const double r2 = 1.4142135623730951;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const bool w0 = r == 0 && q == 0;
+            const double u0 = gc[0][r] + gc[2][r], u1 = gc[0][r] - gc[2][r], v0 = gc[1][r] + gc[3][r], v1 = gc[1][r] - gc[3][r];
+            const double ws = gs[0][r] + gs[2][r], wd = gs[0][r] - gs[2][r], z0 = gs[1][r] + gs[3][r], z1 = gs[1][r] - gs[3][r];
+            const double a0 = r2 * gs[0][r], a2 = r2 * gs[2][r];
+            double* const op8 = gp + (int64_t)(32 * r) * N;
+            op8[0 * N] = u0 + v0;
+            op8[1 * N] = u0 - v0;
+            op8[2 * N] = w0 ? u1 + v1 : ws + z0;
+            op8[3 * N] = w0 ? u1 - v1 : ws - z0;
+            op8[4 * N] = w0 ? a0 + z1 : u1 + z1;
+            op8[5 * N] = w0 ? a0 - z1 : u1 - z1;
+            op8[6 * N] = w0 ? a2 + z0 : v1 - wd;
+            op8[7 * N] = w0 ? a2 - z0 : -wd - v1;
+          }
+        }
+      }
       if constexpr (MUL) fetch(curA, curB, 2);                // (curA / curB already name the next plane)
-      else __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+      else if (!(GX && drained)) __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
+      if (ak_store) {
       // columns 2 (16 jt + lr) + par: wave pair jt = 1 writes the right half (another plane in the quad form); rows >= N / 2 the bottom half
       int64_t ors = g.out_rs;
       asm volatile("" : "+s"(ors));                           // (per plane: keeps the 16 store offsets from being hoisted into 32 live VGPRs)
@@ -783,6 +850,7 @@ __global__ void __launch_bounds__(256, 2) xz_fold_inv_kernel(FoldArgs g) {
           om[(int64_t)(2 * j0 + 1) * ors] = od[r];
         }
       }
+      }   // ak_store
     }
   }
   if constexpr (RED) {
@@ -1429,6 +1497,25 @@ extern "C" int geobo_xz2d_fold_inv_strided(int n, int64_t rows, int planes_per_r
   g.in2 = nullptr; g.in2_row = 0; g.r2_first = 0; g.ss = nullptr;
   dense_inv(g, 64);
   return launch_inv<64, 0>(g, (hipStream_t)stream);
+}
+
+extern "C" int geobo_xz2d_fold_inv_gx(int n, int64_t rows, int planes_per_row, const double* in, int64_t in_row, int64_t in_plane,
+                                      const double* Fx, const double* Fz, double* out, int64_t out_row, int64_t out_plane,
+                                      int store_all, double* gx, int64_t gx_row, int64_t gx_plane, void* stream) {
+  if (!in || !out || !Fx || !Fz || !gx) return GEOBO_E_ARG;
+  if (rows <= 0 || planes_per_row <= 0) return GEOBO_OK;
+  if (gx_plane < 2 * (int64_t)n * n || gx_row < planes_per_row * gx_plane) return GEOBO_E_ARG;
+  if ((in_row & 1) || (in_plane & 1) || ((uintptr_t)in & 15) || ((uintptr_t)Fx & 15) || ((uintptr_t)Fz & 15) || ((uintptr_t)out & 7) ||
+      ((uintptr_t)gx & 7))
+    return GEOBO_E_ALIGN;
+  if (n != 64) return GEOBO_E_UNSUPPORTED;
+  FoldArgs g;
+  g.in = in; g.in_row = in_row; g.in_plane = in_plane; g.out = out; g.out_row = out_row; g.out_plane = out_plane; g.out_rs = n;
+  g.Fz = Fz; g.Fx = Fx; g.ppr = planes_per_row; g.nplanes = rows * planes_per_row;
+  g.row_off = nullptr; g.edge = nullptr; g.in2 = nullptr;
+  g.gx = gx; g.gx_row = gx_row; g.gx_plane = gx_plane; g.gx_all = store_all ? 1 : 0;
+  dense_inv(g, 64);
+  return launch_inv<64, 3>(g, (hipStream_t)stream);
 }
 
 extern "C" int geobo_xz2d_fold_inv_mul(int n, int64_t rows, int planes_per_row, const double* a, int64_t a_plane, const double* b,

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import geometry, hip
-from .plan import COLUMN_FORM_MAX_BYTES, engine_options, plan_route
+from .plan import COLUMN_FORM_MAX_BYTES, engine_options, feed_options, gram_gx_route, plan_route
 from .columnform import ColumnExchangeMixin
 from .rowform import RowFormMixin
 from .operators import StreamedOperator
@@ -58,6 +58,23 @@ from .sharding import (EmulatedGroup, allreduce_sum_, assemble_columns, backend_
 F64 = hip.F64
 
 
+class _GramFeed:
+    """What the spectral product hands the lattice Gram per batch and property block (spectral.SpectralProduct._store): the rows'
+    x analysis GX goes through the Gram's y step, scaling and channel sum at once; the scaled spectra S[block] wait for the
+    back-transform in _assemble_AkA_sym."""
+
+    def __init__(self, gram, lams, S, store_all=True):
+        self.gram, self.lams, self.S, self.store_all = gram, lams, S, store_all
+        self.ld = gram.Py * gram.Px
+
+    def rows(self, jj, r0, R, GX):
+        self.gram.gx_rows(GX, R, self.lams[jj], self.S[jj][r0 * self.ld:])
+
+    def at(self, r0):
+        """The same hand-over for a product that starts at row r0 of the block."""
+        return _GramFeed(self.gram, self.lams, [S[r0 * self.ld:] for S in self.S], self.store_all)
+
+
 class CholeskyError(RuntimeError):
     """AkA not positive definite (first bad pivot in .info, 1-based like LAPACK dpotrf)."""
 
@@ -72,9 +89,16 @@ class FactorisationTimeout(RuntimeError):
 
 
 class _LastStep(dict):
-    """engine.last.  `complete` (set by a mirrored step): fills the rows of A K the step did not compute; run on the first read of the
-    buffer ("AK_partial"), never inside the step."""
+    """engine.last.  `complete` (set by a mirrored step and by a step whose A K product fed the lattice Gram and stored only the
+    boundary planes of its rows): writes what the step left unwritten of A K -- the storing product first, then the mirrored row copy;
+    run on the first read of the buffer ("AK_partial"), never inside the step."""
     complete = None
+
+    @staticmethod
+    def chain(fills):
+        """The completion hook that runs `fills` in order (None for none)."""
+        fills = list(fills)
+        return (lambda: [f() for f in fills] and None) if fills else None
 
     def __getitem__(self, key):
         if key == "AK_partial" and self.complete is not None:
@@ -196,6 +220,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self.route = plan_route(self.nx, self.ny, self.nz, world=world, rank=rank, assembly=assembly, operators=operators, method=method,
                                 env=env)
         self.options = engine_options(env)
+        self.feed = feed_options(env)       # (plan.FEED_OPTIONS: the A K product feeds the lattice Gram, _gram_feed)
         self.use_spectral = self.route.spectral
         if method == "spectral" and not self.use_spectral:
             raise ValueError("spectral method needs grid extents % 16 == 0 and column shards on y-slab boundaries")
@@ -681,13 +706,14 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         if self.exchange:
             return self._assemble_AK_spectral_exchange(step, AK)
         for s_, A in ((0, A_g), (1, A_m)):
-            lams, outs = [], []
+            lams, outs, blocks = [], [], []
             for jj, j in enumerate(props):
                 gen = sp.eigenvalues(step.prior.table(self, s_, j))
                 step.gens[(s_, j)] = gen                # (the transposed posterior path applies the same blocks to L^-1 A_s)
                 if step.sym and (s_, j) not in ((0, 0), (0, 1), (1, 1)):
                     continue
                 lams.append(gen)
+                blocks.append(j)
                 outs.append(AK[s_ * self.Ms_pad:s_ * self.Ms_pad + self.Ms, jj * nc:(jj + 1) * nc])
             # lattice survey, fp64 assembly: the y stage reads the rows as windows of the pool of distinct operator-plane spectra, built
             # here once per operator and step (spectral.plane_pool) -- no forward transform per row
@@ -697,11 +723,14 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             Mrun = step.mirror if (s_ == 1 and step.mirror) else self.Ms
             fl = sp.flops(Mrun, len(lams), y1 - y0, fwd_planes=sp.pool_planes(Mrun) if pooled else None)
             fv = sp.flops_valu(Mrun, len(lams), y1 - y0)
-            if not self.f32 and not isinstance(A, StreamedOperator):
-                self._timed("spectral_product", fl, lambda: sp.product(A, Mrun, lams, [o[:Mrun] for o in outs], y0, y1), valu=fv)
-                continue
+            feed = self._gram_feed(step, s_, blocks) if (y0, y1) == (0, self.ny) else None
+            if feed is not None:
+                fl += self._gram.flops_gx(Mrun * len(lams))
 
-            def batches():
+            def product_rows(gx, A=A, lams=lams, outs=outs, Mrun=Mrun, pooled=pooled):
+                """The block's rows of A K (arguments bound now: the completion hook calls this after the step).  gx: the hand-over."""
+                if not self.f32 and not isinstance(A, StreamedOperator):
+                    return sp.product(A, Mrun, lams, [o[:Mrun] for o in outs], y0, y1, gx=gx)
                 # row batches: operator rows generated on demand (streamed) and / or the product written to an fp64 scratch and
                 # stored as fp32 (fp32 assembly); one batch = the spectral product's own batch size
                 Rb = sp.R
@@ -717,11 +746,29 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                     else:
                         src = A.rows_into(abuf, r0, R) if abuf is not None else A[r0:r0 + R]
                     dst = [b[:R] for b in scr] if scr is not None else [o[r0:r0 + R] for o in outs]
-                    sp.product(src, R, lams, dst, y0, y1)
+                    sp.product(src, R, lams, dst, y0, y1, gx=gx and gx.at(r0))
                     if scr is not None:
                         for jj in range(len(lams)):
                             hip.convert(dst[jj], outs[jj][r0:r0 + R])
-            self._timed("spectral_product", fl, batches, valu=fv)
+            self._timed("spectral_product", fl, lambda: product_rows(feed), valu=fv)
+            if feed is not None and not feed.store_all:
+                step.ak_fill.append(lambda fill=product_rows: fill(None))
+
+    def _gram_feed(self, step, s_, blocks):
+        """The hand-over of x-analysed rows from the A K product of operator s_ to the lattice Gram (options.gram_gx; DESIGN.md 2,
+        "x step in the A K inverse"), or None where the route does not apply: the symmetric plan of the one-rank `single` family, fp64
+        assembly, both operators' Gram on the stencil eigen-data, 64 x 64 (x, z) planes.  Block j of A K meets operator j in AkA."""
+        gram, sp = self._gram, self._spectral_product()
+        funcs = ("grav", "magn")
+        if not (gram_gx_route(self.feed, self.route.family, step.sym, self.f32, self.world, self.exchange, self.nx, self.ny, self.nz, sp.forms)
+                and gram is not None and gram.gx_applies() and sp.gx_applies() and all(j in (0, 1) and self._lam.get(funcs[j]) is not None for j in blocks)):
+            return None
+        S = [self._workspace("gram_S_%d%d" % (s_, j), (self.Ms * gram.Py * gram.Px,)) for j in blocks]
+        for j, Sj in zip(blocks, S):
+            step.gram_S[(s_, j)] = Sj
+        # AkA is the only reader of these rows inside a step (DESIGN.md 2, "Unwritten rows"): of A K the product stores the two
+        # boundary planes (the Gram's edge_rows reads them); the rest is written by step.ak_fill when somebody asks for the buffer
+        return _GramFeed(gram, [self._lam[funcs[j]][1] for j in blocks], S, store_all=False)
 
     def _edge_spectrum(self, func, k, ycols):
         """Spectrum of boundary slab k (0: iy = 0, 1: iy = ny - 1) of operator `func` for the lattice Gram's x-correlation; built once
@@ -1069,11 +1116,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         whole = AK is not None and not step.sym
         self.last = _LastStep(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props,
                               sel=sel, ops=(A_g, A_m), step=step, mv=mv, uu=out.get("uu"), logdet=out.get("logdet"))
+        fills = list(step.ak_fill)           # the hand-over to the Gram stored only the boundary planes of its rows: the storing product first
         if step.mirror and step.mirror < self.Ms:
             # a mirrored step left the magnetic rows behind step.mirror unwritten.  Nothing of the engine reads them (AkA was their only
             # reader); whoever asks for the buffer gets them by the mirrored row copy, once, so that no stale row is ever seen
             jj, nc, Msp, Mm = props.index(1), self.nc, self.Ms_pad, step.mirror
-            self.last.complete = lambda: hip.mirror_rows(AK[Msp:Msp + self.Ms, jj * nc:jj * nc + self.N], self.Ms, Mm, self.nx * self.ny, self.nz)
+            fills.append(lambda: hip.mirror_rows(AK[Msp:Msp + self.Ms, jj * nc:jj * nc + self.N], self.Ms, Mm, self.nx * self.ny, self.nz))
+        self.last.complete = _LastStep.chain(fills)
         return out
 
     def _derivative_gram(self, A_g, A_m, sel_t, prior, slot):

@@ -661,6 +661,23 @@ def ymul(m, k, C, rows, G, src, in_row, out, out_row, fold=False):
                   _p(_chk(out, "out")), int(out_row), _stream()), name)
 
 
+def xz2d_fold_inv_gx(n, rows, ppr, src, in_row, in_plane, Fx, Fz, out, out_row, out_plane, store_all, gx, gx_row, gx_plane):
+    """Inverse radix-4 transform that also emits the lattice Gram's x analysis GX[r][y][o][z] of every interior plane
+    (geobo_xz2d_fold_inv_gx); store_all False: only the two boundary planes of a row are stored to out."""
+    lib = require_gpu()
+    _lib.check(lib.geobo_xz2d_fold_inv_gx(int(n), int(rows), int(ppr), _p(_chk(src, "src")), int(in_row), int(in_plane), _p(_chk(Fx, "Fx")),
+                                          _p(_chk(Fz, "Fz")), _p(_chk(out, "out")), int(out_row), int(out_plane), 1 if store_all else 0,
+                                          _p(_chk(gx, "gx")), int(gx_row), int(gx_plane), _stream()), "geobo_xz2d_fold_inv_gx")
+
+
+def gram_yz(n, ny, rows, gx, gx_row, gx_plane, G, lam_oz, s, s_row, s_plane):
+    """s[r][ky][o] = sum_z lam_oz[ky][o][z] (G gx[r])[ky][o][z]: y step, eigenvalue scaling and channel sum of the lattice Gram on
+    x-analysed rows (geobo_gram_yz); G: (2 ny) x ny pair-interleaved."""
+    lib = require_gpu()
+    _lib.check(lib.geobo_gram_yz(int(n), int(ny), int(rows), _p(_chk(gx, "gx")), int(gx_row), int(gx_plane), _p(_chk(G, "G")), int(G.stride(0)),
+                                 _p(_chk(lam_oz, "lam_oz")), _p(_chk(s, "s")), int(s_row), int(s_plane), _stream()), "geobo_gram_yz")
+
+
 def xcorr_reduce(nx, nz, rows, planes, src, in_row, in_plane, Mx, lam, out, out_row, out_plane):
     """x step + eigenvalue scaling + channel sum of the lattice Gram (geobo_xcorr_reduce)."""
     lib = require_gpu()

@@ -331,6 +331,35 @@ class LatticeGram:
         hy = 0.5 if (f and Ly in self.sp.forms.ymul_slabs) else 1.0     # y step on geobo_ymul_fold: radix 2
         return rows * (2.0 * (hy * hip.pad_n(Py) * nx * nz * Ly + h * Py * Px * nx * nz + hb * (ny * Py * Px + ny * nx * Px)) + zsum)
 
+    # ---- the Gram from x-analysed rows: the inverse transform of the A K product hands over GX instead of the rows -------------------
+    def gx_applies(self):
+        """geobo_gram_yz runs this grid's y step, scaling and channel sum: 64 x 64 (x, z) planes on the radix-4 x kernels, ny <= 64."""
+        return self.sp.forms.gram_x == "fold" and self.nx == 64 and self.nz == 64 and self.ny % 2 == 0 and 4 <= self.ny <= 64
+
+    def gx_rows(self, GX, nrows, lam, S):
+        """S[r][ky][kx] = sum_z lam[ky][z][kx] (Gy0 GX[r])[ky][kx][z] for r < nrows: what the y step and the x step of gram_rows leave
+        in "LG_S", from rows that arrive x-analysed (GX[r][iy][kx][z], spectral.SpectralProduct._store).  S: rows Py*Px doubles apart."""
+        nx, ny, nz, Px, Py = self.nx, self.ny, self.nz, self.Px, self.Py
+        hip.gram_yz(nx, ny, nrows, GX, ny * Px * nz, Px * nz, self.Gy0, self.lam_oz(lam), S, Py * Px, Px)
+
+    def back_rows(self, S, nrows, out):
+        """out[r, :ny*nx] = Gy^T S[r] Gx: the back-transform of gram_rows on spectra that gx_rows left."""
+        for r0 in range(0, nrows, self.R):
+            R = min(self.R, nrows - r0)
+            self._plane_yx(True, R, S[r0 * self.Py * self.Px:], self.Py * self.Px, out[r0:], out.stride(0))
+
+    def flops_gx(self, rows):
+        """Executed MFMA flop of the x analysis inside the inverse transform (radix 4, interior planes) and of gx_rows (radix-2 y step
+        over all 64 k-steps of a tile) for `rows` rows."""
+        nx, ny, nz, Px, Py = self.nx, self.ny, self.nz, self.Px, self.Py
+        return rows * 2.0 * (0.25 * (ny - 2) * Px * nx * nz + 0.5 * hip.pad_n(Py) * 64 * Px * nz)
+
+    def flops_back(self, rows):
+        """Executed flop of back_rows (the back-transform's share of flops())."""
+        nx, ny, Px, Py = self.nx, self.ny, self.Px, self.Py
+        hb = 0.25 if self.sp.forms.gram_x == "fold" else 1.0
+        return rows * 2.0 * hb * (ny * Py * Px + ny * nx * Px)
+
     def gram_rows(self, X, nrows, lam, out, y0=0, y1=None):
         """out[r, :ny*nx] = interior-slab part of (A K)[r] . A^T for r < nrows.  X: (>= nrows x >= (y1-y0)*nx*nz) rows of A K for
         the block's property, voxel columns of the y-slab [y0, y1) only (a rank of a column-sharded run holds just its slab: the

@@ -88,6 +88,28 @@ def engine_options(env=None):
     return EngineOptions(**{k: parse(env[var]) if var in env else default for k, (var, default, parse) in ENGINE_OPTIONS.items()})
 
 
+# The hand-over between the A K product and the lattice Gram (engine._gram_feed): resolved once per engine from the same mapping, beside
+# engine_options().  A table of its own: ENGINE_OPTIONS is pinned entry by entry (tests/test_host_logic_cpu.py::test_engine_options_table),
+# like SWITCHES and Forms, and none of the three moves for it.
+FEED_OPTIONS = {"gram_gx": ("GEOBO_GRAM_GX", True, _on)}      # the A K inverse transform emits the Gram's x analysis; the y spectrum is never stored
+FeedOptions = make_dataclass("FeedOptions", [(k, type(d)) for k, (_, d, _p) in FEED_OPTIONS.items()], frozen=True)
+
+
+def feed_options(env=None):
+    """FeedOptions from an environment-like mapping (None: every default)."""
+    env = {} if env is None else env
+    return FeedOptions(**{k: parse(env[var]) if var in env else default for k, (var, default, parse) in FEED_OPTIONS.items()})
+
+
+def gram_gx_route(opts, family, sym, f32, world, exchange, nx, ny, nz, forms):
+    """Whether a step hands x-analysed rows from the A K product to the lattice Gram: the option, the symmetric plan of the one-rank
+    `single` family, fp64 assembly, and 64 x 64 (x, z) planes on the radix-4 kernels with the dense y stage (what the two kernels,
+    geobo_xz2d_fold_inv_gx and geobo_gram_yz, are instantiated for)."""
+    return bool(opts.gram_gx and sym and family == "single" and not f32 and world == 1 and not exchange
+                and nx == 64 and nz == 64 and ny % 2 == 0 and 4 <= ny <= 64
+                and forms.xz == "fold" and forms.gram_x == "fold" and forms.y != "spectrum")
+
+
 def half_integer(n):
     """True where the axis runs on the HALF-INTEGER (skew-circulant) basis (round 6): a symmetric Toeplitz block of size n is also the
     leading block of the skew-circulant of size P = 2n (first column k_0 .. k_{n-1}, *, -k_{n-1} .. -k_1), diagonalised by cos / sin of

@@ -434,12 +434,40 @@ class SpectralProduct:
                 tabs = y2s[1:] if y2s is not None and y2s[0] == j else None
                 sink(r0, R, js, *self._join(specs, [[g[jj] for jj in js] for _, _, g in terms[:nt]], R, ylo, yhi, tabs, squaring))
 
-    def _store(self, slabs, ylo, yhi):
-        """Sink: the storing inverse transform into rows r0 .. of every slab's targets."""
+    def _store(self, slabs, ylo, yhi, gx=None):
+        """Sink: the storing inverse transform into rows r0 .. of every slab's targets.  gx (gx_applies; one slab, the whole y axis):
+        the inverse transform also emits the lattice Gram's x analysis of every interior plane into the one-batch buffer "GX", and
+        gx.rows(jj, r0, R, GX) consumes it before the next block overwrites it; gx.store_all False: of A K only the two boundary planes
+        of every row are written."""
         def sink(r0, R, js, outs, _):
             for i, jj in enumerate(js):
-                self.backward_xz(outs[i], R, ylo, yhi, [(ya, yb, o[jj][r0:], o[jj].stride(0)) for ya, yb, o in slabs])
+                if gx is None:
+                    self.backward_xz(outs[i], R, ylo, yhi, [(ya, yb, o[jj][r0:], o[jj].stride(0)) for ya, yb, o in slabs])
+                    continue
+                nx, ny, nz, Cp, gp = self.nx, self.ny, self.nz, self.Cp, self.Px * self.nz
+                o = slabs[0][2][jj]
+                GX = self.gx_buffer()
+                hip.xz2d_fold_inv_gx(nx, R, ny, outs[i], ny * Cp, Cp, self.F["x"], self.F["z"], o[r0:], o.stride(0), nx * nz, gx.store_all,
+                                     GX, ny * gp, gp)
+                gx.rows(jj, r0, R, GX)
         return sink
+
+    def gx_applies(self):
+        """The storing inverse transform can emit the lattice Gram's x analysis (geobo_xz2d_fold_inv_gx): the radix-4 kernels of 64 x 64
+        planes behind the dense y stage, at least one interior plane."""
+        return self.forms.xz == "fold" and self.dense_y and self.nx == 64 and self.nz == 64 and self.ny >= 3
+
+    def gx_buffer(self):
+        """GX[R][ny][Px][nz] of one batch.  The inverse transform never writes the two boundary planes of a row and the Gram's y step
+        multiplies them by the zero columns of its matrix: they are zeroed once per allocation, so that they stay finite."""
+        gp = self.Px * self.nz
+        b = self.buf("GX", self.R * self.ny * gp)
+        if getattr(self, "_gx_zeroed", None) != b.data_ptr():
+            v = b[:self.R * self.ny * gp].view(self.R, self.ny, gp)
+            v[:, 0] = 0.0
+            v[:, self.ny - 1] = 0.0
+            self._gx_zeroed = b.data_ptr()
+        return b
 
     def buf(self, name, n):
         b = self._bufs.get(name)
@@ -610,11 +638,12 @@ class SpectralProduct:
         lam.mul_(1.0 / float(self.P3))
         return lam
 
-    def product(self, A, Ms, lam_list, outs, y0=0, y1=None, slabs=None):
+    def product(self, A, Ms, lam_list, outs, y0=0, y1=None, slabs=None, gx=None):
         """outs[j][r, :] = (A[r, :N] convolved with block j) restricted to y-slab [y0,y1), r < Ms.
         A: (>=Ms x N) row-major; outs[j]: 2-D views (rows x (y1-y0)*nx*nz).
         `slabs` = [(y0, y1, outs), ...] crops the SAME scaled spectrum to several y-slabs (one per destination rank of the
-        row-sharded multi-GPU form); the forward passes and the scaling are done once."""
+        row-sharded multi-GPU form); the forward passes and the scaling are done once.
+        gx: the lattice Gram takes the rows' x analysis straight from the inverse transform (_store; gx_applies(), whole y axis)."""
         y1 = self.ny if y1 is None else y1
         if slabs is None:
             slabs = [(y0, y1, outs)]
@@ -625,8 +654,10 @@ class SpectralProduct:
             assert self.forms.lattice_feed
         else:
             assert A.stride(1) == 1 and A.stride(0) >= N and A.stride(0) % 2 == 0
+        if gx is not None:
+            assert self.gx_applies() and len(slabs) == 1 and (slabs[0][0], slabs[0][1]) == (0, self.ny)
         if self.dense_y:
-            return self._product_dense_y(A, Ms, lam_list, slabs)
+            return self._product_dense_y(A, Ms, lam_list, slabs, gx)
         for r0 in range(0, Ms, self.R):
             R = min(self.R, Ms - r0)
             spec = self.forward(A[r0:], R, self.G, src_row_stride=A.stride(0))
@@ -647,11 +678,11 @@ class SpectralProduct:
                         self.backward(s0, R, ya, yb, o[j][r0:], o[j].stride(0))
                     j += 1
 
-    def _product_dense_y(self, A, Ms, gens, slabs):
+    def _product_dense_y(self, A, Ms, gens, slabs, gx=None):
         """z and x through the spectrum, y as Toeplitz blocks: one read of the (x, z)-spectrum per three property blocks."""
         ylo, yhi = min(s[0] for s in slabs), max(s[1] for s in slabs)
         batches = [(r0, min(self.R, Ms - r0), 1) for r0 in range(0, Ms, self.R)]
-        self._drive(batches, [(A, 0, gens)], self._store(slabs, ylo, yhi), ylo, yhi)
+        self._drive(batches, [(A, 0, gens)], self._store(slabs, ylo, yhi, gx), ylo, yhi)
 
     # ---- posterior variance in the transposed order (engine._posterior_zpath) ------------------------------------------------------
     def fused_ss(self):

@@ -92,3 +92,6 @@ class Step:
     # left for the later stages
     gens: dict = field(default_factory=dict)        # Toeplitz generators of the covariance blocks (s, j)
     fullrows: dict = field(default_factory=dict)    # column form with the row exchange: this rank's whole rows of A K
+    gram_S: dict = field(default_factory=dict)      # (s, j) -> the lattice Gram's scaled spectra of the block's rows (engine._gram_feed)
+    ak_fill: list = field(default_factory=list)     # storing products that write the interior planes of A K the hand-over skipped (run by
+                                                    # engine.last's completion hook, on the first read of the buffer)

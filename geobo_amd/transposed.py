@@ -40,8 +40,12 @@ class TransposedPosteriorMixin:
                 return A.edge[:, k * pl:(k + 1) * pl] if A.lattice is not None else A.slab_into(self._workspace2d("op_slab", Msp, pl), iy, iy + 1)
             return A[:, iy * pl:(iy + 1) * pl]
 
-        def rows_times_AT(X, nrows, sp_, out):
-            gram.gram_rows(X, nrows, lam[sp_], out, 0, ny)
+        def rows_times_AT(X, nrows, sp_, out, S=None):
+            # S: the block's rows met the Gram's y and x steps on their way out of the A K product (engine._gram_feed)
+            if S is not None:
+                gram.back_rows(S, nrows, out)
+            else:
+                gram.gram_rows(X, nrows, lam[sp_], out, 0, ny)
             for k, iy in enumerate((0, ny - 1)):
                 gram.edge_rows(X[:, iy * pl:], nrows, self._edge_spectrum(("grav", "magn")[sp_], k, edge_cols(sp_, k, iy)), out)
         blk = lambda r0, j: AK[r0:, props.index(j) * nc:(props.index(j) + 1) * nc]
@@ -51,14 +55,16 @@ class TransposedPosteriorMixin:
         Mm = step.mirror or self.Ms
 
         def run():
-            rows_times_AT(blk(0, 0), self.Ms, 0, AkA[0:, 0:Msp])
-            rows_times_AT(blk(0, 1), self.Ms, 1, AkA[0:, Msp:2 * Msp])
-            rows_times_AT(blk(Msp, 1), Mm, 1, AkA[Msp:, Msp:2 * Msp])
+            rows_times_AT(blk(0, 0), self.Ms, 0, AkA[0:, 0:Msp], S.get((0, 0)))
+            rows_times_AT(blk(0, 1), self.Ms, 1, AkA[0:, Msp:2 * Msp], S.get((0, 1)))
+            rows_times_AT(blk(Msp, 1), Mm, 1, AkA[Msp:, Msp:2 * Msp], S.get((1, 1)))
             hip.transpose(AkA[:Msp, Msp:2 * Msp], AkA[Msp:2 * Msp, :Msp])
             if Md:
                 rows_times_AT(blk(off_d, 0), Md, 0, AkA[off_d:, 0:Msp])
                 rows_times_AT(blk(off_d, 1), Md, 1, AkA[off_d:, Msp:2 * Msp])
-        self._timed("aka_lattice", gram.flops(2 * self.Ms + Mm + 2 * Md, ny), run)
+        S = step.gram_S
+        nfed = sum(self.Ms if s_ == 0 else Mm for s_, _ in S)
+        self._timed("aka_lattice", gram.flops(2 * self.Ms + Mm + 2 * Md - nfed, ny) + gram.flops_back(nfed), run)
         if step.mirror:
             # (after gram_rows AND edge_rows of the block: the fill copies finished rows; same stream, so it is ordered behind them)
             self._timed("aka_centro_fill", 0.0, lambda: hip.centro_fill(AkA[Msp:Msp + self.Ms, Msp:Msp + self.Ms], self.Ms, (self.Ms + 1) // 2))

@@ -399,6 +399,23 @@ int geobo_ymul(int m, int k, int64_t C, int64_t rows, const double* G, int64_t l
 int geobo_ymul_fold(int m, int k, int64_t C, int64_t rows, const double* G, int64_t ldg, const double* in, int64_t in_row,
                     double* out, int64_t out_row, void* stream);
 
+/* Lattice Gram from x-analysed rows (additive, version unchanged).
+ * geobo_xz2d_fold_inv_gx: geobo_xz2d_fold(inverse) whose interior planes (r, y), 0 < y < planes_per_row - 1, also go through the
+ * forward x step of geobo_xcorr_reduce_fold while they are in registers: gx + r*gx_row + y*gx_plane receives GX[o][z] =
+ * sum_x G_x[o][x] X[x][z] (2n x n doubles, o in spectral position order).  The two boundary planes of a row get no GX (their slots
+ * are left untouched).  store_all == 0: only the boundary planes are stored to `out`, the interior planes of `out` are left untouched;
+ * what IS stored equals geobo_xz2d_fold bit for bit.  gx_plane >= 2 n n, gx_row >= planes_per_row * gx_plane (GEOBO_E_ARG).  n = 64.
+ * geobo_gram_yz: s[r*s_row + ky*s_plane + o] = sum_z lam[ky][o][z] * sum_y G[ky][y] gx[r*gx_row + y*gx_plane + o*n + z]  for ky < 2 ny,
+ * o < 2 n, r < rows -- the y step of geobo_ymul_fold (G: (2 ny) x ny pair-interleaved, ldg >= ny; only rows 2b are read), the
+ * eigenvalue scaling and the channel sum of geobo_xcorr_reduce_fold in one launch, the y spectrum never stored.  lam: [2 ny][2 n][n].
+ * Null pointers, gx not 16-byte aligned, odd gx strides, gx_plane < 2 n n, s_plane < 2 n, ny odd or < 2: GEOBO_E_ARG, before any
+ * launch.  n = 64, ny <= 64 (GEOBO_E_UNSUPPORTED otherwise). */
+int geobo_xz2d_fold_inv_gx(int n, int64_t rows, int planes_per_row, const double* in, int64_t in_row, int64_t in_plane,
+                           const double* Fx, const double* Fz, double* out, int64_t out_row, int64_t out_plane, int store_all,
+                           double* gx, int64_t gx_row, int64_t gx_plane, void* stream);
+int geobo_gram_yz(int n, int ny, int64_t rows, const double* gx, int64_t gx_row, int64_t gx_plane, const double* G, int64_t ldg,
+                  const double* lam, double* s, int64_t s_row, int64_t s_plane, void* stream);
+
 /* Folded form of geobo_xcorr_reduce for the pair-interleaved basis in the quarter-period group order of geobo_xz2d_fold (version 210):
  * the x product in RADIX 4 -- one cosine and one sine row per frequency group and residue class of x mod 4, a quarter of the MFMAs of
  * the plain product (rounds 2-4: radix 2, half); F = [n][n/2][2] folded matrices of the x axis (rows 4w, 4w + 1 are read); lamT and out

@@ -52,6 +52,9 @@ DRIVERS = {"posterior": ("run_posterior_once.py", "gemm_f64_kernel<4, 2, 2, 1", 
            "kblock_grid": ("run_k_block_once.py matern32_x f64 grid", "k_block_grid_kernel", "pmc_k_block_grid_f64.json"),
            "fold_inv_ss": ("run_spectral_kernels_once.py fold_inv_ss", "xz_fold_inv_kernel<64, 1,", "pmc_xz2d_fold_inv_ss.json"),
            "fold_inv_strided": ("run_spectral_kernels_once.py fold_inv_strided", "xz_fold_inv_kernel<64, 0,", "pmc_xz2d_fold_inv_strided.json"),
+           "fold_inv_gx": ("run_spectral_kernels_once.py fold_inv_gx", "xz_fold_inv_kernel<64, 3,", "pmc_xz2d_fold_inv_gx.json"),
+           "fold_inv_gx_edge": ("run_spectral_kernels_once.py fold_inv_gx_edge", "xz_fold_inv_kernel<64, 3,", "pmc_xz2d_fold_inv_gx_edge.json"),
+           "gram_yz": ("run_spectral_kernels_once.py gram_yz", "gram_yz_kernel", "pmc_gram_yz.json"),
            "fold_inv_mul": ("run_spectral_kernels_once.py fold_inv_mul", "xz_fold_inv_kernel<64, 2,", "pmc_xz2d_fold_inv_mul.json"),
            "wplanes": ("run_spectral_kernels_once.py wplanes", "lattice_wplanes_kernel", "pmc_lattice_wplanes.json"),
            "colgemv": ("run_spectral_kernels_once.py colgemv", "colgemv_kernel", "pmc_colgemv.json"),

@@ -109,7 +109,8 @@ if which in ("all", "xcorr"):
           lambda: hip.xcorr_reduce(n, n, R, P, src, src.stride(0), n * n, Gx, lam, out, out.stride(0), P))
 # ---- radix-2 / radix-4 kernels: flop = what the folded kernels execute on the matrix pipe (forward: half of the plain product along z,
 # a quarter along x; inverse and xcorr_fold: a quarter) -----------------------------------------------------------------
-if which in ("all", "fold_fwd", "fold_bwd", "xcorr_fold", "fold_inv_ss", "fold_inv_strided", "fold_inv_mul", "fold_conv_fwd", "fold_conv_pair"):
+if which in ("all", "fold_fwd", "fold_bwd", "xcorr_fold", "fold_inv_ss", "fold_inv_strided", "fold_inv_mul", "fold_conv_fwd", "fold_conv_pair",
+             "fold_inv_gx", "fold_inv_gx_edge"):
     import numpy as np
     from geobo_amd.spectral import folded_matrices
     F = hip.to_dev(np.stack(folded_matrices(n), axis=2))
@@ -129,6 +130,25 @@ if which in ("all", "xcorr_fold"):
     out = torch.empty((R, P * P), dtype=torch.float64, device=dev)
     timed("xcorr_fold", R * P * 0.5 * P * n * n, R * P * (n * n + P) * 8.0,
           lambda: hip.xcorr_reduce_fold(n, R, P, src, src.stride(0), n * n, F, lam, out, out.stride(0), P))
+if which in ("all", "fold_inv_gx", "fold_inv_gx_edge"):
+    # the storing inverse transform that also emits the lattice Gram's x analysis of the 62 interior planes of every row (2 nx x nz doubles
+    # each); _edge: of the rows themselves only the two boundary planes are stored
+    src, out = rnd(R, n * P * P), torch.empty((R, n * n * n), dtype=torch.float64, device=dev)
+    gx = torch.empty((R, n * P * n), dtype=torch.float64, device=dev)
+    flop = R * (n * 0.5 * (P * P * n + n * P * n) + (n - 2) * 0.5 * P * n * n)
+    for name, store_all in (("fold_inv_gx", True), ("fold_inv_gx_edge", False)):
+        if which in ("all", name):
+            timed("xz2d_" + name, flop, R * (n * P * P + (n if store_all else 2) * n * n + (n - 2) * P * n) * 8.0,
+                  lambda: hip.xz2d_fold_inv_gx(n, R, n, src, src.stride(0), P * P, F, F, out, out.stride(0), n * n, store_all, gx, gx.stride(0), P * n))
+    del src, out, gx
+if which in ("all", "gram_yz"):
+    # y step + eigenvalue scaling + channel sum on x-analysed rows: reads GX once (the eigenvalues once per workgroup), writes 128 x 128 per row
+    G = rnd(128, 64)
+    gx, lam = rnd(R, n * P * n), rnd(P * P * n)
+    out = torch.empty((R, P * P), dtype=torch.float64, device=dev)
+    timed("gram_yz", R * 1.0 * 128 * 64 * P * n, (R * n * P * n + P * P * n + R * P * P) * 8.0,
+          lambda: hip.gram_yz(n, n, R, gx, gx.stride(0), P * n, G, lam, out, P * P, P))
+    del gx, lam, out
 if which in ("all", "ymul"):
     # y step of the lattice Gram: the (128 x 64) matrix from the left of every (64 x 4096) row; flop = MFMA, bytes = in + out
     G = rnd(128, 64)
