@@ -119,6 +119,9 @@ SIGNATURES = {
                                  _int, _int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
     "geobo_factor_append": (_int, [_int, _dp, _i64, _dp, _i64, _dp, _dp, _i64, _dp, _i64, _dp, _dp, _dp, _dp]),
     "geobo_rows_downdate": (_int, [_dp, _i64, _i64, _i64, _dp, _dp, _dp, _dp]),
+    "geobo_fold_factor": (_int, [_int, _dp, _i64, _dp, _dp, _dp, _i64, _dp, _dp, _dp, _dp]),
+    "geobo_rows_reweight_ws_bytes": (_sz, [_i64]),
+    "geobo_rows_reweight": (_int, [_int, _dp, _i64, _i64, _dp, _i64, _dp, _dp, _dp, _dp, _dp, _sz, _dp]),
     "geobo_trmv_stats": (_int, [_i64, _dp, _i64, _dp, _dp, _i64, _dp, _dp, _dp]),
     "geobo_mfma_f64_peak": (_int, [_int, _int, _dp, _dp]),
     "geobo_mfma_mix": (_int, [_int, _int, _int, _int, _dp, _dp]),

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgeobo_hip.so")
-SOURCES = ["gemm_f64.hip", "gemm_fold.hip", "potrf.hip", "assembly.hip", "toeplitz.hip", "spectral_y.hip", "xz2d.hip", "xz2d_fold.hip", "reduce.hip", "kinv_dot.hip", "sampling.hip", "information.hip", "crossval.hip", "blockcov.hip", "gradetonnage.hip", "geobodies.hip", "intercepts.hip", "append.hip"]
+SOURCES = ["gemm_f64.hip", "gemm_fold.hip", "potrf.hip", "assembly.hip", "toeplitz.hip", "spectral_y.hip", "xz2d.hip", "xz2d_fold.hip", "reduce.hip", "kinv_dot.hip", "sampling.hip", "information.hip", "crossval.hip", "blockcov.hip", "gradetonnage.hip", "geobodies.hip", "intercepts.hip", "append.hip", "reweight.hip"]
 HEADERS = [os.path.join(CSRC, "covfun.h"), os.path.join(CSRC, "cutoff_set.h"), os.path.join(CSRC, "lds_optin.h"), os.path.join(ROOT, "include", "geobo_hip.h")]
 
 

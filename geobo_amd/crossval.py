@@ -109,6 +109,16 @@ def fold_table(folds, Mu=None):
     return tab
 
 
+def without_rows(tab, rows):
+    """The fold table `tab` with the data rows `rows` (dropped by the engine's row scales, reweight.py) left out of every fold: they
+    become padding, live entries first; a fold that loses all its rows stays in the table with size 0 (NaN outputs).  No rows: tab."""
+    rows = np.asarray(rows, dtype=np.int64)
+    if rows.size == 0 or tab.size == 0:
+        return tab
+    tab = np.where(np.isin(tab, rows), -1, tab)
+    return np.take_along_axis(tab, np.argsort(tab < 0, axis=1, kind="stable"), axis=1)
+
+
 def padded_rows(idx, Ms, Ms_pad):
     """Data indices ([grav | magn | drill]) -> rows of the padded matrix (i, Ms_pad + i, 2 Ms_pad + i); padding stays negative."""
     idx = np.asarray(idx, dtype=np.int64)
@@ -132,7 +142,7 @@ class CrossValidationMixin:
             raise RuntimeError("cross_validate() needs the factor of a posterior() step")
         Ms, Msp, Md = self.Ms, self.Ms_pad, len(last["sel"])
         Mu = 2 * Ms + Md
-        tab = fold_table(folds, Mu)
+        tab = without_rows(fold_table(folds, Mu), self.dropped_rows(last["sel"]))
         with torch.cuda.device(self.device):
             return self._cross_validate(tab, last["Linv"], last["u"], Ms, Msp, Mu)
 

@@ -51,6 +51,7 @@ from .resources import ResourceMixin
 from .geobodies import GeobodyMixin
 from .intercepts import InterceptMixin
 from .append import AppendRowsMixin
+from .reweight import ReweightMixin
 from .step import Prior, Step
 from .sharding import (EmulatedGroup, allreduce_sum_, assemble_columns, backend_of, exchange_blocks, exchange_blocks_finish,
                        exchange_blocks_start, gather_rows, gather_slices, shard_columns)
@@ -171,7 +172,7 @@ def _on_device(fn):
 
 
 class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixin, SetStatisticsMixin, CrossValidationMixin, BlockSupportMixin,
-                      PointPredictionMixin, ResourceMixin, GeobodyMixin, InterceptMixin, AppendRowsMixin):
+                      PointPredictionMixin, ResourceMixin, GeobodyMixin, InterceptMixin, AppendRowsMixin, ReweightMixin):
     def __init__(self, settings, device=None, rank=0, world=1, group=None, profile=False, method="auto", assembly="f64",
                  operators="resident"):
         """assembly "f32": covariance tables rounded through fp32 and A K kept in fp32 in HBM (BASELINE config 5, "fp32 kernel
@@ -622,7 +623,11 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
     def _new_step(self, prior, props, sel_t, noise, **kw):
         """A Step over the drill voxels sel_t (int64 device tensor or None); kw: the remaining fields of step.Step."""
         Md = 0 if sel_t is None else sel_t.numel()
-        return Step(prior, tuple(props), sel_t, Md, hip.pad_m(2 * self.Ms_pad + Md), noise, **kw)
+        step = Step(prior, tuple(props), sel_t, Md, hip.pad_m(2 * self.Ms_pad + Md), noise, **kw)
+        if "row_scale" not in kw and self._row_scale_active():
+            # committed row scales (reweight.py) of a step that was not handed them: a derivative Gram of logl_grad
+            step.row_scale = self._step_row_scale(np.zeros(0, dtype=np.int64) if sel_t is None else sel_t.cpu().numpy())
+        return step
 
     def _assemble_AK(self, step, A_g, A_m):
         """A K into the workspace step.ak_slot, or None in the row form (decided here: step.rowpath), which has no A K.
@@ -956,6 +961,19 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             step.prior.k_block(self, 2, 2, rows, rows, AkA[off_d:off_d + Md, off_d:off_d + Md])
             if gp_sigma is not None:
                 dvec[off_d:off_d + Md] = float(gp_sigma[2]) ** 2
+        drop = None
+        if step.row_scale is not None:
+            # committed row scales (reweight.py): s^2 on the noise variance; a dropped row leaves K_y as a zero row and column with a
+            # unit diagonal (a derivative Gram: the zero row and column alone)
+            s2, dropped = step.row_scale
+            if dropped.size:
+                drop = torch.as_tensor(dropped, device=self.device)
+                AkA[drop, :] = 0.0
+                AkA[:, drop] = 0.0
+            if gp_sigma is not None:
+                dvec.mul_(torch.as_tensor(s2, device=self.device))
+                if drop is not None:
+                    dvec[drop] = 1.0
         if gp_sigma is None:
             return AkA
         if step.keep_signal:
@@ -963,12 +981,14 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         AkA.diagonal().add_(dvec)
         return AkA
 
-    def _pad_y(self, y_g, y_m, y_d, M_pad):
+    def _pad_y(self, y_g, y_m, y_d, M_pad, dropped=None):
         y = np.zeros(M_pad)
         y[0:self.Ms] = y_g
         y[self.Ms_pad:self.Ms_pad + self.Ms] = y_m
         if len(y_d):
             y[2 * self.Ms_pad:2 * self.Ms_pad + len(y_d)] = y_d
+        if dropped is not None:
+            y[dropped] = 0.0                    # (rows of the padded matrix that the committed row scales drop, reweight.py)
         return hip.to_dev(y, self.device)
 
     def _results_to_host(self, mu, var, props, queued=None):
@@ -1002,12 +1022,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         sel_t = torch.as_tensor(sel, device=self.device) if sel.size else None
         t = self._tick("start")
         # the data vector goes up first: a pageable host-to-device copy blocks the host until the stream reaches it
-        y = self._pad_y(y_g, y_m, y_d, hip.pad_m(2 * self.Ms_pad + len(sel)))
+        scales = self._step_row_scale(sel)
+        y = self._pad_y(y_g, y_m, y_d, hip.pad_m(2 * self.Ms_pad + len(sel)), None if scales is None else scales[1])
         if self.rows_static and not self._rows_denied and not self._rows_ok(A_g, A_m) and all(f in self._op_args for f in ("grav", "magn")):
             # operators handed in from before a denial / a clear: rebuild them from the recorded arguments in the form this step takes
             A_g, A_m = (self.operator(f, *self._op_args[f][:1], B=self._op_args[f][1], axes=self._op_args[f][2]) for f in ("grav", "magn"))
         step = self._step = self._new_step(Prior(kernelfunc, lengths, weight_matrix(crossweights), gp_amp), props, sel_t, gp_sigma,
-                                           keep_signal=bool(keep_K), sym=not self.rows_static and self._sym_ok(A_g, A_m))
+                                           keep_signal=bool(keep_K), row_scale=scales, sym=not self.rows_static and self._sym_ok(A_g, A_m))
         M_pad = step.M_pad
         step.mirror = self._mirror_rows(step, A_m)
         for f, rec in self.aka_mirror.items():
@@ -1025,6 +1046,10 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
             AkA, self._workspace("Linv", (M_pad, M_pad)), self._workspace("potrf_ws", (hip.potrf_ws_doubles(M_pad),)),
             ctx=self._potrf_ctx, schedule=potrf_schedule or self.options.potrf), alg=(2 * self.Ms + len(sel)) ** 3 * 2.0 / 3.0)  # AkA now holds L
         L = AkA
+        if scales is not None and scales[1].size:
+            # dropped rows: row and column of L^-1 are those of the identity; without the diagonal entry the row is gone from every
+            # product that works from L^-1 (u_i = 0, a zero row of V), and its unit pivot adds nothing to logdet
+            Linv.diagonal()[torch.as_tensor(scales[1], device=self.device)] = 0.0
         self._finish_exchange()
         u, stats = hip.trmv_stats(Linv, y, L)
         t = self._tick("cholesky", t)

@@ -1033,6 +1033,56 @@ def rows_downdate(V, n, c, mu, var, ncols=None):
     return mu, var
 
 
+def fold_factor(G, dinv, a, Cinv, g, stats=None, status=None):
+    """S = G + diag(dinv) (k x k, k <= 128, the lower triangle of G read), S = C C^T, Cinv = C^-1, g = C^-1 a (geobo_fold_factor, one
+    workgroup).  G, Cinv: 2-D fp64 views with unit column stride (k rows and columns used); dinv, a, g: k doubles.  Returns (stats
+    (2,) = [2 sum log diag C, g^T g], status (1,) int32 = 0, or 1 + the failing pivot -- then nothing else was written)."""
+    lib = require_gpu()
+    k = _chk(a, "a").numel()
+    ldg, ldc = _rowmajor(G, "G"), _rowmajor(Cinv, "Cinv")
+    assert all(t.shape[0] >= k and t.shape[1] >= k for t in (G, Cinv)) and a.is_contiguous()
+    assert _chk(dinv, "dinv").numel() == k and dinv.is_contiguous() and _chk(g, "g").numel() >= k and g.is_contiguous()
+    if stats is None:
+        stats = torch.empty(2, dtype=F64, device=G.device)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=G.device)
+    assert _chk(stats, "stats").numel() >= 2 and stats.is_contiguous()
+    _lib.check(lib.geobo_fold_factor(int(k), _p(G), ldg, _p(dinv), _p(a), _p(Cinv), ldc, _p(g), _p(stats), _p(status), _stream()),
+               "geobo_fold_factor")
+    return stats, status
+
+
+def rows_reweight_ws_doubles(ncols):
+    return max(_lib.load().geobo_rows_reweight_ws_bytes(int(ncols)) // 8, 1)
+
+
+def rows_reweight(B, k, Cinv, g, mu=None, var=None, ncols=None, part=None, ws=None):
+    """Per column c < ncols of the first k rows of B: t = Cinv B[:k, c], mu[c] -= t . g, var[c] += t . t (geobo_rows_reweight); returns
+    part (3,) = [sum_c dmu^2, max_c |dmu|, sum_c dvar].  mu = var = None: statistics only, no cube is written.  A tile cut at an even
+    column gives the same mu and var bits; part is summed in a fixed order (no atomics)."""
+    lib = require_gpu()
+    ldb, ldc = _rowmajor(B, "B"), _rowmajor(Cinv, "Cinv")
+    k = int(k)
+    ncols = B.shape[1] if ncols is None else int(ncols)
+    assert 1 <= k <= B.shape[0] and ncols <= B.shape[1] and Cinv.shape[0] >= k and Cinv.shape[1] >= k
+    assert _chk(g, "g").numel() >= k and g.is_contiguous()
+    if (mu is None) != (var is None):
+        raise ValueError("mu and var go together")
+    if mu is not None:
+        assert _chk(mu, "mu").numel() >= ncols and _chk(var, "var").numel() >= ncols and mu.is_contiguous() and var.is_contiguous()
+    if part is None:
+        part = torch.empty(3, dtype=F64, device=B.device)
+    assert _chk(part, "part").numel() >= 3 and part.is_contiguous()
+    need = rows_reweight_ws_doubles(ncols)
+    if ws is None:
+        ws = torch.empty(need, dtype=F64, device=B.device)
+    assert _chk(ws, "ws").numel() >= need and ws.is_contiguous()
+    _lib.check(lib.geobo_rows_reweight(k, _p(B), ldb, ncols, _p(Cinv), ldc, _p(g), None if mu is None else _p(mu),
+                                       None if var is None else _p(var), _p(part), _p(ws), 8 * ws.numel(), _stream()),
+               "geobo_rows_reweight")
+    return part
+
+
 def kinv_diag_ws_doubles(m):
     return max(_lib.load().geobo_kinv_diag_ws_bytes(int(m)) // 8, 1)
 

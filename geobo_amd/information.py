@@ -69,11 +69,12 @@ class SetStatisticsMixin:
             hit = self._set_smp = (key, smp)
         return hit[1]
 
-    def _v_spectral(self, step, prior, Linv, A_g, A_m, blocks=(2,), rows=None):
+    def _v_spectral(self, step, prior, Linv, A_g, A_m, blocks=(2,), rows=None, dense=False):
         """Tiles (Vs, n) of 128 rows of V_a for every property block a of `blocks` in lockstep (Vs: one tile per block) on the
         transposed route, voxel order (iy, ix, iz): the generators of the step whose factor Linv is where it kept them, the others
         from `prior`.  The rows of Z are formed once per tile and every operator term is ONE product for all the blocks (Z is
-        transformed once).  rows = (r0, r1): the rows r0 .. r1 only (_tile_range)."""
+        transformed once).  rows = (r0, r1): the rows r0 .. r1 only (_tile_range).  dense: Linv is a dense left factor (rows of K_y^-1,
+        reweight.py), not a lower triangular one: no operator term is skipped."""
         sel_t, Md = step.sel_t, step.Md
         sp, N, Msp, T = self._spectral, self.N, self.Ms_pad, 128
         lat = (self._gram is not None and self._gram.edge_supported() and Msp == self.nx * self.ny and self.route.opt("z_lattice")
@@ -92,14 +93,14 @@ class SetStatisticsMixin:
             n = min(T, r1 - b0)
             terms = []
             for func, A, Ar, c0, Z, g in (("grav", A_g, None if lat else Ag, 0, Zg, gens[0]), ("magn", A_m, None if lat else Am, Msp, Zm, gens[1])):
-                if b0 + n <= c0:
+                if not dense and b0 + n <= c0:
                     continue                                # L^-1 is lower triangular: these rows do not see this operator
                 if lat:
                     self._lattice_Z(Linv[b0:b0 + n, c0:c0 + Msp], n, func, A, Z)
                 else:
                     hip.gemm_nn(Linv[b0:b0 + T, c0:c0 + Msp], Ar[:Msp, :N], Z)
                 terms.append((Z, g))
-            if Md and b0 + n > 2 * Msp:
+            if Md and (dense or b0 + n > 2 * Msp):
                 Zd[:n].zero_()
                 Zd[:n, sel_t] = Linv[b0:b0 + n, 2 * Msp:2 * Msp + Md]
                 terms.append((Zd, gens[2]))
@@ -110,9 +111,10 @@ class SetStatisticsMixin:
                     v[:n].add_(t[:n])
             yield _tile_rows(V, n, r0 - b0)
 
-    def _v_generic(self, step, prior, Linv, A_g, A_m, AK, blocks=(2,), rows=None):
+    def _v_generic(self, step, prior, Linv, A_g, A_m, AK, blocks=(2,), rows=None, dense=False):
         """Tiles (Vs, n) of 256 rows of V_a for every property block a of `blocks` on any one-rank fp64 step, voxel order
-        (iy, ix, iz).  Vs[i] holds N columns or more.  rows = (r0, r1): the rows r0 .. r1 only (_tile_range)."""
+        (iy, ix, iz).  Vs[i] holds N columns or more.  rows = (r0, r1): the rows r0 .. r1 only (_tile_range).  dense: Linv is a dense
+        left factor, not a lower triangular one: the contraction runs over every row of A K and no operator term is skipped."""
         sel_t, Md = step.sel_t, step.Md
         N, Np, Msp, T = self.N, self.N_pad, self.Ms_pad, 256
         r0, r1 = _tile_range(rows, 2 * Msp + Md)
@@ -123,7 +125,10 @@ class SetStatisticsMixin:
             for b0 in range(start, r1, T):
                 e = b0 + T                                  # (M_pad is a multiple of 256: whole tiles; columns >= e of L^-1 are zero)
                 for AKd, v in zip(AKa, V):
-                    hip.gemm_nn(Linv[b0:e, :e], AKd[:e], v)
+                    if dense:
+                        hip.gemm_nn(Linv[b0:e], AKd, v)
+                    else:
+                        hip.gemm_nn(Linv[b0:e, :e], AKd[:e], v)
                 yield _tile_rows(V, min(T, r1 - b0), r0 - b0)
             return
         smp = self._set_sampler(prior)
@@ -132,14 +137,14 @@ class SetStatisticsMixin:
         for b0 in range(start, r1, T):
             n = min(T, r1 - b0)
             for j, A, a0 in ((0, A_g, 0), (1, A_m, Msp)):
-                if b0 + n <= a0:
+                if not dense and b0 + n <= a0:
                     Zt[:, j, :].zero_()
                     continue
                 for c0, arows in self._operator_rows(A):
                     hip.gemm_nn(Linv[b0:b0 + T, a0 + c0:a0 + c0 + arows.shape[0]], arows, Zp, beta=1.0 if c0 else 0.0)
                 Zt[:, j, :] = Zp[:, :N]
             Zt[:, 2, :].zero_()
-            if Md and b0 + n > 2 * Msp:
+            if Md and (dense or b0 + n > 2 * Msp):
                 Zt[:, 2, :][:, sel_t] = Linv[b0:b0 + T, 2 * Msp:2 * Msp + Md]
             KZ = smp.apply_K(Zt[:n])                        # (all three properties come out of the one circulant product)
             yield _tile_rows([KZ[:, a, :] for a in blocks], n, r0 - b0)
@@ -156,12 +161,17 @@ class SetStatisticsMixin:
         self.set_source = source
         return source
 
-    def _v_tiles(self, source, prior, AK, blocks=(2,), rows=None):
+    def _v_tiles(self, source, prior, AK, blocks=(2,), rows=None, left=None):
         """Generator of the V tiles of the last step's factor from `source` ("spectral" or "generic"); rows = (r0, r1): the rows
-        r0 .. r1 of V only (default: all of them)."""
+        r0 .. r1 of V only (default: all of them).  left: a dense left factor in the place of L^-1 (rows of K_y^-1 padded to the
+        tile height, reweight.py): the tiles are rows of left A3 K and the short-cuts of a triangular factor are off."""
         last = self.last
         Linv, step = last["Linv"], last["step"]
         A_g, A_m = last["ops"]
+        if left is not None:
+            if source == "spectral":
+                return self._v_spectral(step, prior, left, A_g, A_m, blocks, rows, dense=True)
+            return self._v_generic(step, prior, left, A_g, A_m, AK if last["AK_complete"] else None, blocks, rows, dense=True)
         if source == "spectral":
             return self._v_spectral(step, prior, Linv, A_g, A_m, blocks, rows)
         return self._v_generic(step, prior, Linv, A_g, A_m, AK if last["AK_complete"] else None, blocks, rows)

@@ -423,6 +423,183 @@ class Inversion:
             var = [var_cubes[i] * scale[i] ** 2 for i in range(3)]
         return rec[0], rec[1], rec[2], var[0], var[1], var[2]
 
+    # ---- down-weighting or dropping data rows -------------------------------------------------------------
+    def _data_rows(self, grav=None, magn=None, drill=None):
+        """Indices into the data vector [grav | magn | drill] of stations and drill rows named per data type: grav, magn: station
+        indices; drill: drill row indices or a (k, 3) array of voxel indices (iy, ix, iz) that carry a drill value."""
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("the rows of a survey are those of cubing(): call cubing() first")
+        s = self.settings
+        ng, nm, nd = self.gravfield.size, self.magfield.size, self.Fs3.size - self.gravfield.size - self.magfield.size
+        out = []
+        for name, v, off, n in (("grav", grav, 0, ng), ("magn", magn, ng, nm), ("drill", drill, ng + nm, nd)):
+            if v is None:
+                continue
+            v = np.asarray(v)
+            if v.size and not np.issubdtype(v.dtype, np.integer):
+                raise ValueError("%s must hold integer indices" % name)
+            if name == "drill" and v.ndim == 2 and v.shape[1] == 3:
+                if np.any(v < 0) or np.any(v >= np.array([s.yNcube, s.xNcube, s.zNcube])):
+                    raise ValueError("voxel indices (iy, ix, iz) must lie inside the (%d, %d, %d) cube" % (s.yNcube, s.xNcube, s.zNcube))
+                flat = (v[:, 0].astype(np.int64) * s.xNcube + v[:, 1]) * s.zNcube + v[:, 2]
+                order = np.argsort(self._sel)
+                pos = np.searchsorted(self._sel[order], flat)
+                pos = np.minimum(pos, max(nd - 1, 0))
+                if nd == 0 or np.any(self._sel[order][pos] != flat):
+                    raise ValueError("a voxel named in drill carries no drill value")
+                v = order[pos]
+            v = v.reshape(-1).astype(np.int64)
+            if np.any(v < 0) or np.any(v >= n):
+                raise ValueError("%s indices must lie in [0, %d)" % (name, n))
+            out.append(v + off)
+        rows = np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+        if rows.size < 1:
+            raise ValueError("no data row is named")
+        if np.unique(rows).size != rows.size:
+            raise ValueError("a row is named twice")
+        return rows
+
+    def _stepped_with_mean(self):
+        """The engine's factor at the current hyper-parameters with its likelihood, mean and variance (one whole step otherwise)."""
+        self._ensure_factor()
+        if self.engine.last.get("uu") is None or not self.engine.mean_var_known():
+            self._run(self.gp_amp, self.gp_length, None, True, True)
+
+    def _change_statistics(self, sum_dmu2, max_dmu, sum_dvar):
+        """Per property, in cubing()'s units: RMS and largest change of the mean cube, mean increase of the variance."""
+        N = self.engine.N
+        sc = np.array([float(v) for v in self._cube_scale])
+        with np.errstate(all="ignore"):
+            return dict(rms_change=np.sqrt(np.asarray(sum_dmu2) / N) * sc, max_change=np.asarray(max_dmu) * sc,
+                        mean_var_increase=np.asarray(sum_dvar) / N * sc ** 2)
+
+    def _six_cubes(self, mu, var):
+        s = self.settings
+        shape = (3, s.yNcube, s.xNcube, s.zNcube)
+        mean_cubes, var_cubes = np.asarray(mu).reshape(shape), np.asarray(var).reshape(shape)
+        scale = self._cube_scale
+        with np.errstate(all="ignore"):
+            return tuple(mean_cubes[i] * scale[i] for i in range(3)) + tuple(var_cubes[i] * scale[i] ** 2 for i in range(3))
+
+    def reweight_data(self, grav=None, magn=None, drill=None, scale=np.inf, commit=False, write=False):
+        """The cubes without (scale=inf, the default) or with less weight on (scale > 1: that many times the noise standard
+        deviation, a scalar or one per named row in the order grav, magn, drill) some data rows, after cubing().  grav, magn: station
+        indices; drill: drill row indices or (k, 3) voxel indices (iy, ix, iz).
+        commit=False: a preview from the factor the step left on the device -- no new step, nothing changes; at most 128 rows.
+        commit=True: the scales are recorded (on top of those committed before; restore_data() clears them), ONE step runs with them,
+        mu_rec, cov_rec and logl follow, and every later step and every product that works from the factor sees the reduced system;
+        any number of rows.  The survey stays the full x-y lattice either way: the step keeps its lattice forms.
+        Returns dict(cubes: the six cubes in cubing()'s units, logl, delta_logl, rows, and per property rms_change, max_change (of the
+        mean cube) and mean_var_increase).  write=True: cube_<...>_dropped.vtk in outpath."""
+        rows = self._data_rows(grav, magn, drill)
+        from .reweight import check_scales
+        sc = check_scales(scale, rows.size)
+        eng = self.engine
+        if not commit:
+            self._stepped_with_mean()
+        logl0 = float(self.logl)
+        if not commit:
+            r = eng.reweight_preview(rows, sc, want="cubes")
+            h = eng._to_host(torch.cat([r["mu"].reshape(-1), r["var"].reshape(-1)]), 0)
+            mu, var, logl = h[:3 * eng.N].copy(), h[3 * eng.N:].copy(), r["logl"]
+            stats = self._change_statistics(r["sum_dmu2"], r["max_dmu"], r["sum_dvar"])
+        else:
+            if np.any(sc == 1.0):
+                raise ValueError("a scale of 1 changes nothing: leave the row out")
+            ng, nm = self.gravfield.size, self.magfield.size
+            cur = eng._data_scales(self._sel)
+            if np.any(np.isinf(cur[rows])):
+                raise ValueError("rows %s are dropped already" % rows[np.isinf(cur[rows])][:8])
+            cur[rows] = cur[rows] * sc
+            rs = eng.row_scale
+            per_voxel = np.ones(eng.N) if rs is None else rs["drill"].copy()
+            per_voxel[self._sel] = cur[ng + nm:]
+            mu0, var0 = np.asarray(self.mu_rec, dtype=np.float64), np.asarray(np.diag(self.cov_rec), dtype=np.float64)
+            eng.set_row_scale(cur[:ng], cur[ng:ng + nm], per_voxel)
+            try:
+                r = self._run(self.gp_amp, self.gp_length, None, True, True)
+            except Exception:
+                eng.row_scale = rs
+                self._step_params = None
+                raise
+            mu, var, logl = r["mu"], r["var"], r["logl"]
+            self.mu_rec, self.cov_rec, self.logl = mu, DiagonalCovariance(var), logl
+            d = (mu - mu0).reshape(3, -1)
+            stats = self._change_statistics((d ** 2).sum(axis=1), np.abs(d).max(axis=1), (var - var0).reshape(3, -1).sum(axis=1))
+        out = dict(cubes=self._six_cubes(mu, var), logl=float(logl), delta_logl=float(logl) - logl0, rows=rows, **stats)
+        if write:
+            self._write_dropped_cubes(out["cubes"])
+        return out
+
+    def _write_dropped_cubes(self, cubes):
+        import os
+
+        from . import dataio
+        s = self.settings
+        origin = (self.voxelpos[0].min(), self.voxelpos[1].min(), self.voxelpos[2].min())
+        names = ["cube_density", "cube_magsus", "cube_drill", "cube_density_variance", "cube_magsus_variance", "cube_drill_variance"]
+        for c, n in zip(cubes, names):
+            dataio.create_vtkcube(c, origin, (s.xvoxsize, s.yvoxsize, s.zvoxsize), fname=os.path.join(s.outpath, n + "_dropped.vtk"))
+
+    def restore_data(self):
+        """Clear every committed row scale: the next step runs on the whole survey again and returns the bits it returned before
+        the first reweight_data(commit=True).  The factor on the device is marked stale (the next product rebuilds it)."""
+        self.engine.set_row_scale()
+        self._step_params = None
+
+    def _row_sigma(self):
+        """Noise standard deviation per data row with the committed row scales (a dropped row: 0 -- it is not in the system)."""
+        ng, nm = self.gravfield.size, self.magfield.size
+        sig = np.concatenate([np.full(ng, float(self.gp_sigma[0])), np.full(nm, float(self.gp_sigma[1])),
+                              np.full(self.Fs3.size - ng - nm, float(self.gp_sigma[2]))])
+        if self._engine is None or self._engine.row_scale is None:
+            return sig
+        sc = self._engine._data_scales(self._sel)
+        return np.where(np.isinf(sc), 0.0, sig * np.where(np.isinf(sc), 1.0, sc))
+
+    def fold_influence(self, folds="holes", cell=None, write=False):
+        """For every fold of cross_validate's fold definitions ("loo", "holes", "patches" or a list of index arrays into the data
+        vector, at most 128 rows each), what the model would look like WITHOUT it, from the statistics-only preview (no step, no
+        cube): a pandas table, one row per fold, with FOLD, SIZE, FIRST_ROW, DELTA_LOGL (log-likelihood of the remaining data minus
+        that of all the data) and per property RMS_<p>, MAX_<p> (RMS and largest change of the mean cube) and DVAR_<p> (mean increase
+        of the variance), in cubing()'s units, sorted by the summed relative RMS change (largest first; RANK).  Rows that are dropped
+        already are in no fold.  write=True: fold_influence.csv in outpath."""
+        import pandas as pd
+
+        from .resources import PROPS
+        self._check_cv_folds(folds)
+        if not hasattr(self, "Fs3") or not hasattr(self, "_cube_scale"):
+            raise RuntimeError("fold_influence() works from the survey of cubing(): call cubing() first")
+        eng = self.engine
+        self._ensure_factor()
+        if eng.last.get("uu") is None:
+            self._run(self.gp_amp, self.gp_length, None, True, True)
+        st = eng.last.get("append")
+        uu, logdet = (st["uu"], st["logdet"]) if st is not None else (eng.last["uu"], eng.last["logdet"])
+        logl0 = -0.5 * (uu + logdet + eng.N * np.log(2 * np.pi))
+        rec = []
+        for c, fold in enumerate(self._cv_folds(folds, cell)):
+            fold = np.asarray(fold, dtype=np.int64).reshape(-1)
+            fold = fold[fold >= 0]
+            r = eng.reweight_preview(fold, np.inf, want="stats")
+            ch = self._change_statistics(r["sum_dmu2"], r["max_dmu"], r["sum_dvar"])
+            row = dict(FOLD=c, SIZE=fold.size, FIRST_ROW=int(fold.min()), DELTA_LOGL=r["logl"] - logl0)
+            for i, p in enumerate(PROPS):
+                row.update({"RMS_" + p.upper(): ch["rms_change"][i], "MAX_" + p.upper(): ch["max_change"][i],
+                            "DVAR_" + p.upper(): ch["mean_var_increase"][i]})
+            rec.append(row)
+        table = pd.DataFrame(rec)
+        if len(table):
+            sc = np.array([float(v) for v in self._cube_scale])
+            with np.errstate(all="ignore"):
+                score = np.nansum(np.stack([table["RMS_" + p.upper()].to_numpy() / sc[i] for i, p in enumerate(PROPS)]), axis=0)
+            table = table.iloc[np.argsort(-score, kind="stable")].reset_index(drop=True)
+            table.insert(0, "RANK", np.arange(1, len(table) + 1))
+        if write:
+            import os
+            table.to_csv(os.path.join(self.settings.outpath, "fold_influence.csv"), index=False)
+        return table
+
     # ---- posterior realisations (DESIGN.md section 12) ---------------------------------------------------------------------------
     def _prior_sampler(self, approximate):
         """PriorSampler of the current hyper-parameters (cached per grid, kernel, lengths, weights, amplitude)."""
@@ -485,7 +662,7 @@ class Inversion:
         ng, nm = self.gravfield.size, self.magfield.size
         y_g, y_m, y_d = self.Fs3[:ng], self.Fs3[ng:ng + nm], self.Fs3[ng + nm:]
         M = ng + nm + y_d.size
-        sig = np.concatenate([np.full(ng, float(self.gp_sigma[0])), np.full(nm, float(self.gp_sigma[1])), np.full(y_d.size, float(self.gp_sigma[2]))])
+        sig = self._row_sigma()
         sig_t = torch.as_tensor(sig, dtype=torch.float64, device=eng.device)
         n, start = int(n), int(start)
         # conditioning transforms two samples per complex line: sample k always shares it with sample k ^ 1 (batches start at even
@@ -798,11 +975,18 @@ class Inversion:
         if not isinstance(folds, str):
             return folds
         if folds == "loo":
-            return crossval.loo_folds(self.Fs3.size)
-        if folds == "holes":
-            return crossval.hole_folds(self._sel, s.zNcube, Ms)
-        cell = 2.0 * s.xvoxsize if cell is None else float(cell)
-        return crossval.patch_folds(np.asarray(self.sensor_locations, dtype=float)[:, :2], cell, Ms, sel=self._sel, nz=s.zNcube)
+            out = crossval.loo_folds(self.Fs3.size)
+        elif folds == "holes":
+            out = crossval.hole_folds(self._sel, s.zNcube, Ms)
+        else:
+            cell = 2.0 * s.xvoxsize if cell is None else float(cell)
+            out = crossval.patch_folds(np.asarray(self.sensor_locations, dtype=float)[:, :2], cell, Ms, sel=self._sel, nz=s.zNcube)
+        dropped = self._engine.dropped_rows(self._sel) if self._engine is not None else np.zeros(0, dtype=np.int64)
+        if dropped.size:
+            # rows the committed row scales drop are in no fold; a fold that is left empty goes
+            out = [f[~np.isin(f, dropped)] for f in (np.asarray(f, dtype=np.int64).reshape(-1) for f in out)]
+            out = [f for f in out if f.size]
+        return out
 
     def _check_cv_folds(self, folds):
         if isinstance(folds, str) and folds not in self.CV_FOLDS:
@@ -830,9 +1014,7 @@ class Inversion:
             self._run(self.gp_amp, self.gp_length, None, False, False)
         r = {k: v.cpu().numpy() for k, v in eng.cross_validate(self._cv_folds(folds, cell)).items()}
         ng, nm, Mu = self.gravfield.size, self.magfield.size, self.Fs3.size
-        sig = np.concatenate([np.full(ng, float(self.gp_sigma[0])), np.full(nm, float(self.gp_sigma[1])),
-                              np.full(Mu - ng - nm, float(self.gp_sigma[2]))])
-        fit = sig ** 2 * r["alpha"]
+        fit = self._row_sigma() ** 2 * r["alpha"]
         out = dict(fit_residual=fit, folds={k: r[k] for k in ("logp", "mahalanobis", "size", "status")})
         summary = dict(logp=float(np.sum(r["logp"])))
         # the type of a fold: that of all its rows (a fold over several types counts for none)

@@ -49,6 +49,13 @@ def run(settings, method="auto", bayesopt=True, write=True):
             if write:
                 for c, n in zip(updated, names):
                     dataio.create_vtkcube(c, origin, voxelsize, fname=os.path.join(s.outpath, n + "_updated.vtk"))
+    dropped = None
+    dd = getattr(s, "drop_data", None)                    # optional YAML key drop_data: {grav: [...], magn: [...], drill: [...]} -- stations
+    if dd:                                                # and drill rows the model is to be shown WITHOUT: the scales
+        dropped = inv.reweight_data(grav=dd.get("grav"), magn=dd.get("magn"), drill=dd.get("drill"), commit=True)      # are committed,
+        if write:                                         # one step follows, and every product below works from the reduced system
+            for c, n in zip(dropped["cubes"], names):
+                dataio.create_vtkcube(c, origin, voxelsize, fname=os.path.join(s.outpath, n + "_dropped.vtk"))
     cv = getattr(s, "cross_validate", None)               # optional YAML key cross_validate: loo | holes | patches
     if cv:
         cv_result = inv.cross_validate(folds=str(cv), write=write)
@@ -56,6 +63,9 @@ def run(settings, method="auto", bayesopt=True, write=True):
     if updated is not None:
         out.update({n + "_updated": c for n, c in zip(names, updated)}, assimilated_voxels=new_vox)
         cubes = updated                                   # (the proposals below look at the cubes with the new values in)
+    if dropped is not None:
+        out.update({n + "_dropped": c for n, c in zip(names, dropped["cubes"])}, dropped_data=dropped)
+        cubes = dropped["cubes"]                          # (... and without the dropped rows)
     if cv:
         out["cross_validation"] = cv_result
     bm = getattr(s, "block_model", None)                  # optional YAML key block_model: [bx, by, bz] voxels per block

@@ -85,6 +85,7 @@ class Step:
     ak_slot: str = "AK"         # workspaces of A K and AkA (a derivative Gram keeps its own beside the step's)
     aka_slot: str = "AkA"
     keep_signal: bool = False   # copy AkA before its diagonal into workspace "K_signal" (the signal part of K: logl_grad)
+    row_scale: object = None    # the engine's committed row scales for this step's rows (reweight._step_row_scale); None: all ones
     # decided by the A K assembly
     sym: bool = False           # only the blocks of A K that AkA's lower triangle needs (transposed order on a lattice survey)
     rowpath: bool = False       # the row-sharded form: no A K at all

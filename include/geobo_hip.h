@@ -884,6 +884,30 @@ int geobo_factor_append(int k, const double* D, int64_t ldd, const double* G, in
  * any device access (GEOBO_E_ARG): NULL mu or var, NULL V or c with n > 0, n < 0, ncols < 0, ld < ncols, ncols > 2^38. */
 int geobo_rows_downdate(const double* V, int64_t ld, int64_t n, int64_t ncols, const double* c, double* mu, double* var, void* stream);
 
+/* ---- down-weighting or dropping rows of a factorised K_y (reweight.hip) -----------------------------------
+ * geobo_fold_factor: S = G + diag(dinv) (k x k, k <= 128; the LOWER triangle of G is read, leading dimension ldg; dinv: k doubles,
+ * 0 for a dropped row), Cholesky S = C C^T in LDS, C^-1 in place, one workgroup:
+ *   Cinv (k x k, leading dimension ldc): C^-1, lower triangular, the strict upper triangle of the k x k block written as zero;
+ *   g = C^-1 a (k; a: k doubles),   stats[0] = 2 sum log diag C,   stats[1] = g^T g,   status[0] = 0;
+ * or status[0] = 1 + the first pivot that is not positive and finite, and NOTHING else is written.  Checks before any device access
+ * (GEOBO_E_ARG): NULL pointers, k < 1, k > 128, a leading dimension < k. */
+int geobo_fold_factor(int k, const double* G, int64_t ldg, const double* dinv, const double* a, double* Cinv, int64_t ldc, double* g,
+                      double* stats, int* status, void* stream);
+
+/* geobo_rows_reweight: for c < ncols, over the k rows of B (k x ldb fp64 row-major, ldb >= ncols), with Cinv (lower triangular, k x k,
+ * leading dimension ldc) and g as geobo_fold_factor leaves them:
+ *     t_r = sum_{q <= r} Cinv[r, q] B[q, c]  (ascending q),   dmu = -sum_r t_r g_r,   dvar = sum_r t_r^2  (ascending r, one fma each),
+ *     mu[c] += dmu,   var[c] += dvar,      part = (sum_c dmu^2, max_c |dmu|, sum_c dvar).
+ * mu == var == NULL: statistics only, nothing but part and ws is written (the same part bits).  A thread owns two adjacent columns and
+ * loads 16 bytes where B, mu and var are 16-byte aligned and ldb is even, one column and 8 bytes otherwise (the same arithmetic per
+ * column: a tile cut at an even column gives the same mu and var bits).  part goes through one partial per workgroup in ws
+ * (geobo_rows_reweight_ws_bytes(ncols) bytes, 8-byte aligned) and a finishing launch that adds them in index order: no atomics.
+ * Checks before any device access: NULL B, Cinv, g, part or ws, one of mu and var NULL alone, k < 1, k > 128, ncols < 0, ldb < ncols,
+ * ldc < k, ncols > 2^38, ws_bytes too small (GEOBO_E_ARG); ws not 8-byte aligned (GEOBO_E_ALIGN). */
+size_t geobo_rows_reweight_ws_bytes(int64_t ncols);
+int geobo_rows_reweight(int k, const double* B, int64_t ldb, int64_t ncols, const double* Cinv, int64_t ldc, const double* g, double* mu,
+                        double* var, double* part, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
