@@ -32,6 +32,7 @@ SIGNATURES = {
     "geobo_centro_fill": (_int, [_dp, _i64, _i64, _i64, _dp]),
     "geobo_transpose": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _dp]),
     "geobo_mirror_rows": (_int, [_dp, _i64, _i64, _i64, _i64, _int, _dp]),
+    "geobo_mirror_planes": (_int, [_dp, _i64, _dp, _i64, _i64, _i64, _i64, _int, _int, _dp]),
     "geobo_mirror_dev_ws_bytes": (_sz, []),
     "geobo_mirror_dev": (_int, [_dp, _i64, _dp, _i64, _i64, _int, _int, _dp, _dp, _sz, _dp]),
     "geobo_colgemv_ws_bytes": (_sz, [_i64, _i64]),

@@ -17,6 +17,8 @@
 //   geobo_transpose     dst = src^T, tiled through LDS: the lower-left block of AkA from the upper-right one the lattice Gram computed.
 //   geobo_mirror_rows   the same point mirror on rows of A K (voxel blocks of nz doubles reversed, z kept): for readers of the rows
 //                       the step did not compute.
+//   geobo_mirror_planes ... on ONE (x, z) plane of every row, between two buffers: the boundary planes of the mirrored rows of A_m K_10
+//                       (the lattice Gram's boundary-slab term reads nothing else of them).
 //   geobo_mirror_dev    max |a - mirror(b)| and max |a|, |b| of a lattice operator's stencil table / boundary slabs: the measurement
 //                       that decides whether geobo_centro_fill may stand for the product.  Slot-owned partial maxima + one finishing
 //                       pass, no atomics.
@@ -130,6 +132,18 @@ __global__ void __launch_bounds__(256) mirror_rows_kernel(double* __restrict__ X
     reinterpret_cast<v2d*>(X + r * ld)[e] = reinterpret_cast<const v2d*>(X + (m - 1 - r) * ld)[se];
 }
 
+// dst[m-1-r][x][:] = src[r][nx-1-x][:] for r0 <= r < r1: ONE (x, z) plane per row under the point mirror (the y index is the caller's:
+// src and dst point at opposite boundary planes of the rows).  One thread per 16-byte pair of the destination plane.
+__global__ void __launch_bounds__(256) mirror_planes_kernel(const double* __restrict__ src, int64_t lds, double* __restrict__ dst, int64_t ldd,
+                                                            int64_t m, int64_t r0, int64_t r1, int nx, int nz2) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)nx * nz2) return;
+  const int64_t x = e / nz2;
+  const int64_t se = (nx - 1 - x) * nz2 + (e - x * nz2);
+  for (int64_t r = r0 + blockIdx.y; r < r1; r += gridDim.y)
+    reinterpret_cast<v2d*>(dst + (m - 1 - r) * ldd)[e] = reinterpret_cast<const v2d*>(src + r * lds)[se];
+}
+
 // NaN-keeping maximum: a NaN anywhere makes the result NaN (the gate that reads it then says no)
 __device__ __forceinline__ double max_keep_nan(double m, double v) { return (v > m || v != v) ? v : m; }
 
@@ -231,6 +245,18 @@ extern "C" int geobo_mirror_rows(double* X, int64_t ld, int64_t m, int64_t r0, i
   const int64_t pairs = nb * (nz / 2), gy = m - r0 < 65535 ? m - r0 : 65535;
   hipLaunchKernelGGL(mirror_rows_kernel, dim3((unsigned)((pairs + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, X, ld, m, r0, nb,
                      nz / 2);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
+
+extern "C" int geobo_mirror_planes(const double* src, int64_t lds, double* dst, int64_t ldd, int64_t m, int64_t r0, int64_t r1, int nx, int nz,
+                                   void* stream) {
+  if (!src || !dst || m < 0 || r0 < 0 || r0 > r1 || r1 > m || nx <= 0 || nz <= 0 || (int64_t)nx * nz > lds || (int64_t)nx * nz > ldd)
+    return GEOBO_E_ARG;
+  if ((nz & 1) || (lds & 1) || (ldd & 1) || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return GEOBO_E_ALIGN;
+  if (r0 == r1) return GEOBO_OK;
+  const int64_t pairs = (int64_t)nx * (nz / 2), gy = r1 - r0 < 65535 ? r1 - r0 : 65535;
+  hipLaunchKernelGGL(mirror_planes_kernel, dim3((unsigned)((pairs + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, src, lds, dst,
+                     ldd, m, r0, r1, nx, nz / 2);
   return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
 }
 

@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import geometry, hip
-from .plan import COLUMN_FORM_MAX_BYTES, engine_options, feed_options, gram_gx_route, plan_route
+from .plan import COLUMN_FORM_MAX_BYTES, cross_options, cross_rows_route, engine_options, feed_options, gram_gx_route, plan_route
 from .columnform import ColumnExchangeMixin
 from .rowform import RowFormMixin
 from .operators import StreamedOperator
@@ -222,6 +222,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                                 env=env)
         self.options = engine_options(env)
         self.feed = feed_options(env)       # (plan.FEED_OPTIONS: the A K product feeds the lattice Gram, _gram_feed)
+        self.cross = cross_options(env)     # (plan.CROSS_OPTIONS: which rows give AkA's cross block, plan.cross_rows_route)
         self.use_spectral = self.route.spectral
         if method == "spectral" and not self.use_spectral:
             raise ValueError("spectral method needs grid extents % 16 == 0 and column shards on y-slab boundaries")
@@ -710,16 +711,19 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         y0, y1 = self.c0 // plane, self.c1 // plane
         if self.exchange:
             return self._assemble_AK_spectral_exchange(step, AK)
+        # the symmetric plan: the blocks the buffer keeps for its readers (engine.last["AK_partial"]), and the blocks the step runs -- the
+        # same, or with AkA's cross block from the magnetic rows (step.cross_rows): A_m K_10 on the step.mirror rows the
+        # magnetic block runs anyway in place of A_g K_01 on every gravity row
+        kept = ((0, 0), (0, 1), (1, 1))
+        run = ((0, 0), (1, 0), (1, 1)) if step.cross_rows == "magn" else kept
         for s_, A in ((0, A_g), (1, A_m)):
-            lams, outs, blocks = [], [], []
+            gen_of, out_of = {}, {}
             for jj, j in enumerate(props):
-                gen = sp.eigenvalues(step.prior.table(self, s_, j))
-                step.gens[(s_, j)] = gen                # (the transposed posterior path applies the same blocks to L^-1 A_s)
-                if step.sym and (s_, j) not in ((0, 0), (0, 1), (1, 1)):
-                    continue
-                lams.append(gen)
-                blocks.append(j)
-                outs.append(AK[s_ * self.Ms_pad:s_ * self.Ms_pad + self.Ms, jj * nc:(jj + 1) * nc])
+                gen_of[j] = sp.eigenvalues(step.prior.table(self, s_, j))
+                step.gens[(s_, j)] = gen_of[j]          # (the transposed posterior path applies the same blocks to L^-1 A_s)
+                out_of[j] = AK[s_ * self.Ms_pad:s_ * self.Ms_pad + self.Ms, jj * nc:(jj + 1) * nc]
+            blocks = [j for j in props if not step.sym or (s_, j) in run]
+            lams, outs = [gen_of[j] for j in blocks], [out_of[j] for j in blocks]
             # lattice survey, fp64 assembly: the y stage reads the rows as windows of the pool of distinct operator-plane spectra, built
             # here once per operator and step (spectral.plane_pool) -- no forward transform per row
             pooled = (isinstance(A, StreamedOperator) and A.lattice is not None and A.lattice.jy is not None and not self.f32
@@ -756,8 +760,13 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                         for jj in range(len(lams)):
                             hip.convert(dst[jj], outs[jj][r0:r0 + R])
             self._timed("spectral_product", fl, lambda: product_rows(feed), valu=fv)
-            if feed is not None and not feed.store_all:
-                step.ak_fill.append(lambda fill=product_rows: fill(None))
+            # what the buffer's readers are owed of this operator's rows and the step did not store whole: the hand-over's interior planes,
+            # and with the cross block from the magnetic rows A_g K_01, which the step did not run
+            whole = feed is None or feed.store_all
+            late = [j for j in props if (not step.sym or (s_, j) in kept) and not (whole and j in blocks)]
+            if late:
+                step.ak_fill.append(lambda fill=product_rows, lams=[gen_of[j] for j in late], outs=[out_of[j] for j in late]:
+                                    fill(None, lams=lams, outs=outs))
 
     def _gram_feed(self, step, s_, blocks):
         """The hand-over of x-analysed rows from the A K product of operator s_ to the lattice Gram (options.gram_gx; DESIGN.md 2,
@@ -1031,6 +1040,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                                            keep_signal=bool(keep_K), row_scale=scales, sym=not self.rows_static and self._sym_ok(A_g, A_m))
         M_pad = step.M_pad
         step.mirror = self._mirror_rows(step, A_m)
+        step.cross_rows = "magn" if cross_rows_route(self.cross, step.sym, step.mirror, self.nx, self.ny, self.nz) else "grav"
         for f, rec in self.aka_mirror.items():
             rec["taken"] = bool(f == "magn" and step.mirror)      # (only the magnetic block has a mirrored form; gravity measures "no")
         AK = self._assemble_AK(step, A_g, A_m)
@@ -1141,14 +1151,18 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         whole = AK is not None and not step.sym
         self.last = _LastStep(L=L, Linv=Linv, u=u, AK=AK if whole else None, AK_partial=None if whole else AK, AK_complete=whole, props=props,
                               sel=sel, ops=(A_g, A_m), step=step, mv=mv, uu=out.get("uu"), logdet=out.get("logdet"))
-        fills = list(step.ak_fill)           # the hand-over to the Gram stored only the boundary planes of its rows: the storing product first
+        self.last.complete = self._ak_completion(step, AK)
+        return out
+
+    def _ak_completion(self, step, AK):
+        """engine.last's completion hook for the A K buffer of a finished step (None: nothing was left unwritten)."""
+        fills = list(step.ak_fill)           # the storing products of what the step did not store whole (_assemble_AK_spectral) first
         if step.mirror and step.mirror < self.Ms:
             # a mirrored step left the magnetic rows behind step.mirror unwritten.  Nothing of the engine reads them (AkA was their only
             # reader); whoever asks for the buffer gets them by the mirrored row copy, once, so that no stale row is ever seen
-            jj, nc, Msp, Mm = props.index(1), self.nc, self.Ms_pad, step.mirror
+            jj, nc, Msp, Mm = step.props.index(1), self.nc, self.Ms_pad, step.mirror
             fills.append(lambda: hip.mirror_rows(AK[Msp:Msp + self.Ms, jj * nc:jj * nc + self.N], self.Ms, Mm, self.nx * self.ny, self.nz))
-        self.last.complete = _LastStep.chain(fills)
-        return out
+        return _LastStep.chain(fills)
 
     def _derivative_gram(self, A_g, A_m, sel_t, prior, slot):
         """A derivative Gram dK in workspace `slot`: posterior()'s own assembly (_assemble_AK / _assemble_AkA, whichever route the

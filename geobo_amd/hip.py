@@ -250,6 +250,17 @@ def mirror_rows(X, m, r0, nb, nz):
     return X
 
 
+def mirror_planes(src, dst, m, r0, r1, nx, nz):
+    """dst[m-1-r, (x, z)] = src[r, (nx-1-x, z)] for r0 <= r < r1 (geobo_mirror_planes): one (x, z) plane per row under the point mirror.
+    src, dst: 2-D row-major views starting at the plane read / written, at least m rows and nx*nz columns; they must not overlap."""
+    lib = require_gpu()
+    lds, ldd = _rowmajor(src, "src"), _rowmajor(dst, "dst")
+    assert src.shape[0] >= r1 and dst.shape[0] >= m and src.shape[1] >= nx * nz and dst.shape[1] >= nx * nz
+    _lib.check(lib.geobo_mirror_planes(_p(src), int(lds), _p(dst), int(ldd), int(m), int(r0), int(r1), int(nx), int(nz), _stream()),
+               "geobo_mirror_planes")
+    return dst
+
+
 def mirror_dev_ws_doubles():
     return require_gpu().geobo_mirror_dev_ws_bytes() // 8
 

@@ -110,6 +110,36 @@ def gram_gx_route(opts, family, sym, f32, world, exchange, nx, ny, nz, forms):
                 and forms.xz == "fold" and forms.gram_x == "fold" and forms.y != "spectrum")
 
 
+# Which rows give AkA's cross block (engine._assemble_AK_spectral, transposed._assemble_AkA_sym): resolved once
+# per engine from the same mapping.  Again a table of its own: ENGINE_OPTIONS, SWITCHES, Forms and FEED_OPTIONS are pinned entry by entry.
+CROSS_ROWS = ("auto", "magn", "grav")
+
+
+def _cross_rows(v):
+    if v not in CROSS_ROWS:
+        raise ValueError("GEOBO_CROSS_ROWS must be one of %s, got %r" % (", ".join(CROSS_ROWS), v))
+    return v
+
+
+CROSS_OPTIONS = {"cross_rows": ("GEOBO_CROSS_ROWS", "auto", _cross_rows)}     # "magn": the mirrored half of the magnetic rows; "grav": all gravity rows
+CrossOptions = make_dataclass("CrossOptions", [(k, type(d)) for k, (_, d, _p) in CROSS_OPTIONS.items()], frozen=True)
+
+
+def cross_options(env=None):
+    """CrossOptions from an environment-like mapping (None: every default)."""
+    env = {} if env is None else env
+    return CrossOptions(**{k: parse(env[var]) if var in env else default for k, (var, default, parse) in CROSS_OPTIONS.items()})
+
+
+def cross_rows_route(opts, sym, mirror_rows, nx, ny, nz):
+    """Whether a step builds AkA's cross block from the magnetic rows A_m K_10 it runs anyway: the symmetric plan with the magnetic
+    point mirror taken (mirror_rows > 0: the operator measured as its own mirror), and the option.  "auto" takes it on the planner's
+    cube only (nx = ny = nz = 64, the grids of Forms.zx) -- a restriction of the roll-out, not of the method."""
+    if not (sym and mirror_rows) or opts.cross_rows == "grav":
+        return False
+    return opts.cross_rows == "magn" or nx == ny == nz == 64
+
+
 def half_integer(n):
     """True where the axis runs on the HALF-INTEGER (skew-circulant) basis (round 6): a symmetric Toeplitz block of size n is also the
     leading block of the skew-circulant of size P = 2n (first column k_0 .. k_{n-1}, *, -k_{n-1} .. -k_1), diagonalised by cos / sin of

@@ -90,6 +90,7 @@ class Step:
     sym: bool = False           # only the blocks of A K that AkA's lower triangle needs (transposed order on a lattice survey)
     rowpath: bool = False       # the row-sharded form: no A K at all
     mirror: int = 0             # > 0 (sym only): magnetic rows the assembly runs; the rest of AkA's magnetic block is their point mirror
+    cross_rows: str = "grav"    # rows behind AkA's cross block: "grav" (A_g K_01, all rows) | "magn" (A_m K_10, the step.mirror rows; plan.cross_rows_route)
     # left for the later stages
     gens: dict = field(default_factory=dict)        # Toeplitz generators of the covariance blocks (s, j)
     fullrows: dict = field(default_factory=dict)    # column form with the row exchange: this rank's whole rows of A K

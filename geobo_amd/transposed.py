@@ -40,31 +40,56 @@ class TransposedPosteriorMixin:
                 return A.edge[:, k * pl:(k + 1) * pl] if A.lattice is not None else A.slab_into(self._workspace2d("op_slab", Msp, pl), iy, iy + 1)
             return A[:, iy * pl:(iy + 1) * pl]
 
-        def rows_times_AT(X, nrows, sp_, out, S=None):
+        def interior(X, nrows, sp_, out, S=None):
             # S: the block's rows met the Gram's y and x steps on their way out of the A K product (engine._gram_feed)
             if S is not None:
                 gram.back_rows(S, nrows, out)
             else:
                 gram.gram_rows(X, nrows, lam[sp_], out, 0, ny)
+
+        def slabs(X, nrows, sp_, out):
             for k, iy in enumerate((0, ny - 1)):
                 gram.edge_rows(X[:, iy * pl:], nrows, self._edge_spectrum(("grav", "magn")[sp_], k, edge_cols(sp_, k, iy)), out)
+
+        def rows_times_AT(X, nrows, sp_, out, S=None):
+            interior(X, nrows, sp_, out, S)
+            slabs(X, nrows, sp_, out)
         blk = lambda r0, j: AK[r0:, props.index(j) * nc:(props.index(j) + 1) * nc]
 
         # step.mirror: A K holds the first rows of the magnetic block only (engine._assemble_AK_spectral); the block is centrosymmetric
         # (operator measured: engine._mirror_record), so its remaining rows are the point mirror of the computed ones
         Mm = step.mirror or self.Ms
+        cross = step.cross_rows == "magn"
+
+        def cross_from_magn():
+            """AkA[magn rows, grav columns] from the step.mirror rows of A_m K_10 ("cross block from the magnetic rows"): row
+            Ms-1-r of A_m K_10 is the point mirror of row r.  The interior slabs meet the gravity stencil table, which the Gram models as
+            even in both offsets, so that part of row Ms-1-r is row r's with the sensor index reversed: a point mirror of the square
+            block.  Gravity's boundary slabs have no such symmetry: they take the mirrored rows' own boundary planes (the x-reversed
+            opposite planes of their partners) and are added behind the fill, for every row.  Then the upper-right block by transpose."""
+            X, out, Ms = blk(Msp, 0), AkA[Msp:, 0:Msp], self.Ms
+            interior(X, Mm, 0, out, S.get((1, 0)))
+            hip.centro_fill(out[:Ms, :Ms], Ms, (Ms + 1) // 2)
+            for dst, src in ((0, ny - 1), (ny - 1, 0)):
+                hip.mirror_planes(X[:, src * pl:(src + 1) * pl], X[:, dst * pl:(dst + 1) * pl], Ms, 0, Ms - Mm, self.nx, self.nz)
+            slabs(X, Ms, 0, out)
+            hip.transpose(AkA[Msp:2 * Msp, :Msp], AkA[:Msp, Msp:2 * Msp])
 
         def run():
             rows_times_AT(blk(0, 0), self.Ms, 0, AkA[0:, 0:Msp], S.get((0, 0)))
-            rows_times_AT(blk(0, 1), self.Ms, 1, AkA[0:, Msp:2 * Msp], S.get((0, 1)))
+            if not cross:
+                rows_times_AT(blk(0, 1), self.Ms, 1, AkA[0:, Msp:2 * Msp], S.get((0, 1)))
             rows_times_AT(blk(Msp, 1), Mm, 1, AkA[Msp:, Msp:2 * Msp], S.get((1, 1)))
-            hip.transpose(AkA[:Msp, Msp:2 * Msp], AkA[Msp:2 * Msp, :Msp])
+            if cross:
+                cross_from_magn()
+            else:
+                hip.transpose(AkA[:Msp, Msp:2 * Msp], AkA[Msp:2 * Msp, :Msp])
             if Md:
                 rows_times_AT(blk(off_d, 0), Md, 0, AkA[off_d:, 0:Msp])
                 rows_times_AT(blk(off_d, 1), Md, 1, AkA[off_d:, Msp:2 * Msp])
         S = step.gram_S
         nfed = sum(self.Ms if s_ == 0 else Mm for s_, _ in S)
-        self._timed("aka_lattice", gram.flops(2 * self.Ms + Mm + 2 * Md - nfed, ny) + gram.flops_back(nfed), run)
+        self._timed("aka_lattice", gram.flops((self.Ms + 2 * Mm if cross else 2 * self.Ms + Mm) + 2 * Md - nfed, ny) + gram.flops_back(nfed), run)
         if step.mirror:
             # (after gram_rows AND edge_rows of the block: the fill copies finished rows; same stream, so it is ordered behind them)
             self._timed("aka_centro_fill", 0.0, lambda: hip.centro_fill(AkA[Msp:Msp + self.Ms, Msp:Msp + self.Ms], self.Ms, (self.Ms + 1) // 2))

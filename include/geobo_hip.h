@@ -601,6 +601,14 @@ int geobo_transpose(int64_t rows, int64_t cols, const double* src, int64_t lds, 
  *     X[r][b][z] = X[m-1-r][nb-1-b][z]   for r0 <= r < m, b < nb voxel columns (iy, ix), z < nz
  * 2 r0 >= m, nb nz <= ld (GEOBO_E_ARG); nz, ld even, X 16-byte aligned (GEOBO_E_ALIGN). */
 int geobo_mirror_rows(double* X, int64_t ld, int64_t m, int64_t r0, int64_t nb, int nz, void* stream);
+/* Additive, version unchanged.  The same mirror on ONE (x, z) plane per row, between two buffers with row strides of their own:
+ *     dst[m-1-r][x][z] = src[r][nx-1-x][z]   for r0 <= r < r1, x < nx, z < nz
+ * src / dst point at the plane read / written in row 0; the y index is the caller's (the boundary plane iy = 0 of a mirrored row of
+ * A_m K_10 is the x-reversed plane iy = ny-1 of its partner and the other way round: two calls).  The planes read and the planes
+ * written must not overlap; rows of dst outside m-1-r1 < row <= m-1-r0 are not touched.  0 <= r0 <= r1 <= m, nx nz <= lds, ldd
+ * (GEOBO_E_ARG, also for a null pointer); nz, lds, ldd even, src, dst 16-byte aligned (GEOBO_E_ALIGN). */
+int geobo_mirror_planes(const double* src, int64_t lds, double* dst, int64_t ldd, int64_t m, int64_t r0, int64_t r1, int nx, int nz,
+                        void* stream);
 /* Whether an operator HAS that symmetry is measured, not assumed:
  *     out2[0] = max |a[r][x][z] - b[rows-1-r][nx-1-x][z]|,   out2[1] = max(|a|, |b|)   over r < rows, x < nx, z < nz
  * (a NaN in either makes the result NaN).  a, b: rows of nx nz doubles, lda / ldb apart.  For the stencil table
