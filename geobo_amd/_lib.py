@@ -33,6 +33,8 @@ SIGNATURES = {
     "geobo_transpose": (_int, [_i64, _i64, _dp, _i64, _dp, _i64, _dp]),
     "geobo_mirror_rows": (_int, [_dp, _i64, _i64, _i64, _i64, _int, _dp]),
     "geobo_mirror_planes": (_int, [_dp, _i64, _dp, _i64, _i64, _i64, _i64, _int, _int, _dp]),
+    "geobo_sym_add": (_int, [_i64, _dp, _i64, _dp, _i64, _dp]),
+    "geobo_slab_pair_y": (_int, [_int, _i64, _i64, _i64, _dp, _i64, _dp, _dp, _i64, _dp]),
     "geobo_mirror_dev_ws_bytes": (_sz, []),
     "geobo_mirror_dev": (_int, [_dp, _i64, _dp, _i64, _i64, _int, _int, _dp, _dp, _sz, _dp]),
     "geobo_colgemv_ws_bytes": (_sz, [_i64, _i64]),

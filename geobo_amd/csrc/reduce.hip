@@ -15,6 +15,8 @@
 //   geobo_centro_fill   B[r][c] = B[n-1-r][n-1-c] for r >= r0: the second half of a centrosymmetric block of AkA (inversion.py:96) from its
 //                       first half -- the magnetic block of a row-major lattice survey under a vertical field.  Stream copy.
 //   geobo_transpose     dst = src^T, tiled through LDS: the lower-left block of AkA from the upper-right one the lattice Gram computed.
+//   geobo_sym_add       B += E + E^T on a square block, the transposed tiles through LDS: the two boundary-slab cross terms of AkA's
+//                       gravity block from ONE sweep of the lattice Gram's slab stage ("gravity block from half its rows").
 //   geobo_mirror_rows   the same point mirror on rows of A K (voxel blocks of nz doubles reversed, z kept): for readers of the rows
 //                       the step did not compute.
 //   geobo_mirror_planes ... on ONE (x, z) plane of every row, between two buffers: the boundary planes of the mirrored rows of A_m K_10
@@ -219,7 +221,30 @@ __global__ void __launch_bounds__(256) transpose_kernel(int64_t rows, int64_t co
     if (c0 + i < cols && r0 + tx < rows) dst[(c0 + i) * ldd + r0 + tx] = t[tx][i];
 }
 
+// B[r][c] += E[r][c] + E[c][r]: the tile (r0, c0) of B takes the tile of E in place and the tile (c0, r0) of E through LDS, as
+// transpose_kernel reads it.  Every element of B has one owner: no atomics.
+__global__ void __launch_bounds__(256) sym_add_kernel(int64_t n, const double* __restrict__ E, int64_t lde, double* __restrict__ B, int64_t ldb) {
+  __shared__ double t[64][65];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t r0 = (int64_t)blockIdx.y * 64, c0 = (int64_t)blockIdx.x * 64;
+#pragma unroll 4
+  for (int i = ty; i < 64; i += 4)
+    if (c0 + i < n && r0 + tx < n) t[i][tx] = E[(c0 + i) * lde + r0 + tx];
+  __syncthreads();
+#pragma unroll 4
+  for (int i = ty; i < 64; i += 4)
+    if (r0 + i < n && c0 + tx < n) B[(r0 + i) * ldb + c0 + tx] += E[(r0 + i) * lde + c0 + tx] + t[tx][i];
+}
+
 }  // namespace
+
+extern "C" int geobo_sym_add(int64_t n, const double* E, int64_t lde, double* B, int64_t ldb, void* stream) {
+  if (!E || !B || n < 0 || lde < n || ldb < n || (n + 63) / 64 > 65535) return GEOBO_E_ARG;
+  if (n == 0) return GEOBO_OK;
+  const unsigned nt = (unsigned)((n + 63) / 64);
+  hipLaunchKernelGGL(sym_add_kernel, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, n, E, lde, B, ldb);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}
 
 extern "C" int geobo_transpose(int64_t rows, int64_t cols, const double* src, int64_t lds, double* dst, int64_t ldd, void* stream) {
   if (!src || !dst || rows < 0 || cols < 0 || lds < cols || ldd < rows || (rows + 63) / 64 > 65535) return GEOBO_E_ARG;

@@ -718,3 +718,43 @@ extern "C" int geobo_toeplitz_y3(int ny, int64_t C, int64_t plane, int64_t R, in
   for (int j = 0; j < 3; ++j) { g.tab[j] = tabs[j < nprop ? j : 0]; g.out[j] = outs[j < nprop ? j : 0]; }
   return launch_win_by_ny<false>(ny, g, (hipStream_t)stream);
 }
+
+// ---- the two boundary planes of rows that live on those planes only (geobo_slab_pair_y) ------------------------------------------------
+// A row whose planes 1 .. ny-2 are zero meets T_c in four of its entries: per mode c
+//     out[r][0][c] = t_c(0) in[r][0][c] + t_c(ny-1) in[r][1][c],      out[r][1][c] = t_c(ny-1) in[r][0][c] + t_c(0) in[r][1][c]
+// (index 0 / 1: the planes y = 0 / ny-1).  One pass: a lane owns two adjacent modes (16-byte accesses), keeps its four table values in
+// registers and walks the rows blockIdx.y, blockIdx.y + gridDim.y, ...
+namespace {
+typedef double sp_v2d __attribute__((ext_vector_type(2)));
+
+__global__ void __launch_bounds__(256) slab_pair_y_kernel(int64_t rows, int64_t C2, int64_t S, const double* __restrict__ in, int64_t in_row,
+                                                          const double* __restrict__ t0, const double* __restrict__ t1, double* __restrict__ out,
+                                                          int64_t out_row) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;      // mode pair
+  if (p >= C2) return;
+  const sp_v2d a = reinterpret_cast<const sp_v2d*>(t0)[p], b = reinterpret_cast<const sp_v2d*>(t1)[p];
+#pragma unroll 2
+  for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    const sp_v2d e0 = reinterpret_cast<const sp_v2d*>(in + r * in_row)[p], e1 = reinterpret_cast<const sp_v2d*>(in + r * in_row + S)[p];
+    sp_v2d o0, o1;
+    o0.x = __builtin_fma(b.x, e1.x, a.x * e0.x);
+    o0.y = __builtin_fma(b.y, e1.y, a.y * e0.y);
+    o1.x = __builtin_fma(a.x, e1.x, b.x * e0.x);
+    o1.y = __builtin_fma(a.y, e1.y, b.y * e0.y);
+    reinterpret_cast<sp_v2d*>(out + r * out_row)[p] = o0;
+    reinterpret_cast<sp_v2d*>(out + r * out_row + S)[p] = o1;
+  }
+}
+}  // namespace
+
+extern "C" int geobo_slab_pair_y(int ny, int64_t C, int64_t plane, int64_t rows, const double* in, int64_t in_row, const double* tab, double* out,
+                                 int64_t out_row, void* stream) {
+  if (!in || !tab || !out || ny < 2 || rows < 0 || C <= 0 || plane < C || in_row < 2 * plane || out_row < 2 * plane) return GEOBO_E_ARG;
+  if ((C & 1) || (plane & 1) || (in_row & 1) || (out_row & 1) || ((uintptr_t)in & 15) || ((uintptr_t)tab & 15) || ((uintptr_t)out & 15))
+    return GEOBO_E_ALIGN;
+  if (rows == 0) return GEOBO_OK;
+  const int64_t C2 = C / 2, gy = rows < 256 ? rows : 256;      // (the table values are loaded once per 16 rows at Ms = 4096)
+  hipLaunchKernelGGL(slab_pair_y_kernel, dim3((unsigned)((C2 + 255) / 256), (unsigned)gy), dim3(256), 0, (hipStream_t)stream, rows, C2, plane, in,
+                     in_row, tab, tab + (int64_t)(ny - 1) * C, out, out_row);
+  return hipGetLastError() == hipSuccess ? GEOBO_OK : GEOBO_E_LAUNCH;
+}

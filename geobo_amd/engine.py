@@ -38,7 +38,8 @@ import numpy as np
 import torch
 
 from . import geometry, hip
-from .plan import COLUMN_FORM_MAX_BYTES, cross_options, cross_rows_route, engine_options, feed_options, gram_gx_route, plan_route
+from .plan import (COLUMN_FORM_MAX_BYTES, cross_options, cross_rows_route, engine_options, feed_options, gram_gx_route, grav_mirror_route,
+                   grav_options, plan_route)
 from .columnform import ColumnExchangeMixin
 from .rowform import RowFormMixin
 from .operators import StreamedOperator
@@ -223,6 +224,7 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         self.options = engine_options(env)
         self.feed = feed_options(env)       # (plan.FEED_OPTIONS: the A K product feeds the lattice Gram, _gram_feed)
         self.cross = cross_options(env)     # (plan.CROSS_OPTIONS: which rows give AkA's cross block, plan.cross_rows_route)
+        self.grav = grav_options(env)       # (plan.GRAV_OPTIONS: AkA's gravity block from half its rows, plan.grav_mirror_route)
         self.use_spectral = self.route.spectral
         if method == "spectral" and not self.use_spectral:
             raise ValueError("spectral method needs grid extents % 16 == 0 and column shards on y-slab boundaries")
@@ -730,22 +732,56 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                       and sp.pool_applies())
             # mirrored magnetic block (step.mirror): only the rows whose AkA rows are computed; the others are never written
             Mrun = step.mirror if (s_ == 1 and step.mirror) else self.Ms
-            fl = sp.flops(Mrun, len(lams), y1 - y0, fwd_planes=sp.pool_planes(Mrun) if pooled else None)
+            # gravity block from half its rows (step.grav_mirror): the interior part A_i of the first rows runs -- their windows
+            # of the pool between two zero planes; resident rows: copies with the two planes zeroed --, the boundary slabs of every row are
+            # still transformed (the slab-slab term)
+            half = bool(s_ == 0 and step.grav_mirror)
+            if half:
+                Mrun = step.grav_mirror
+            fl = sp.flops(Mrun, len(lams), y1 - y0, fwd_planes=sp.pool_planes(self.Ms if half else Mrun) if pooled else None)
             fv = sp.flops_valu(Mrun, len(lams), y1 - y0)
             feed = self._gram_feed(step, s_, blocks) if (y0, y1) == (0, self.ny) else None
+            assert not half or ((pooled or not isinstance(A, StreamedOperator)) and feed is not None and not feed.store_all and blocks == [0])      # (the gate: _grav_mirror_rows)
             if feed is not None:
                 fl += self._gram.flops_gx(Mrun * len(lams))
 
-            def product_rows(gx, A=A, lams=lams, outs=outs, Mrun=Mrun, pooled=pooled):
-                """The block's rows of A K (arguments bound now: the completion hook calls this after the step).  gx: the hand-over."""
+            def product_rows(gx, A=A, lams=lams, outs=outs, Mrun=Mrun, pooled=pooled, half=half):
+                """The block's rows of A K (arguments bound now: the completion hook calls this after the step).  gx: the hand-over.
+                half: the interior part of the rows only; planes 0 and ny-1 of the boundary part's product go to step.grav_slabs."""
+                slabs_to = lambda: self._workspace2d("grav_slabs", self.Ms + 1, 2 * plane)[:self.Ms]      # (a row of slack: edge_rows)
+
+                def keep_planes():
+                    # planes 0 and ny-1 of the rows of A_i K the product just stored, compact and apart from the A K buffer: the
+                    # completion hook overwrites the buffer's with the whole rows', and AkA may be assembled again after it
+                    P = self._workspace2d("grav_iplanes", self.Ms + 1, 2 * plane)[:self.Ms]
+                    P[:Mrun, :plane].copy_(outs[0][:Mrun, :plane])
+                    P[:Mrun, plane:].copy_(outs[0][:Mrun, (self.ny - 1) * plane:self.ny * plane])
+                    step.grav_iplanes = P
                 if not self.f32 and not isinstance(A, StreamedOperator):
-                    return sp.product(A, Mrun, lams, [o[:Mrun] for o in outs], y0, y1, gx=gx)
+                    if not half:
+                        return sp.product(A, Mrun, lams, [o[:Mrun] for o in outs], y0, y1, gx=gx)
+                    # resident rows: the same operands as the pooled feed's -- the slab spectra of every row from the operator's own
+                    # planes 0 and ny-1, the interior part as a batch copy of the rows with those two planes zeroed
+                    step.grav_slabs = sp.slab_pair_rows(sp.slab_spectra(A, self.Ms), self.Ms, lams[0], slabs_to())
+                    abuf = self._op_rows_buffer()
+                    for r0 in range(0, Mrun, sp.R):
+                        R = min(sp.R, Mrun - r0)
+                        abuf[:R, :self.N].copy_(A[r0:r0 + R, :self.N])
+                        abuf[:R, :plane].zero_()
+                        abuf[:R, (self.ny - 1) * plane:self.ny * plane].zero_()
+                        sp.product(abuf, R, lams, [o[r0:r0 + R] for o in outs], y0, y1, gx=gx and gx.at(r0))
+                    return keep_planes()
                 # row batches: operator rows generated on demand (streamed) and / or the product written to an fp64 scratch and
                 # stored as fp32 (fp32 assembly); one batch = the spectral product's own batch size
                 Rb = sp.R
                 abuf = self._op_rows_buffer() if isinstance(A, StreamedOperator) else None
                 scr = [self._workspace2d("ak_rows64_%d" % jj, Rb, nc) for jj in range(len(lams))] if self.f32 else None
-                pool = sp.plane_pool(A.lattice, Mrun, A.lattice.jy, A.lattice.jx) if pooled else None
+                pool = sp.plane_pool(A.lattice, self.Ms if half else Mrun, A.lattice.jy, A.lattice.jx) if pooled else None
+                if half:
+                    step.grav_slabs = sp.slab_pair_rows(pool.edge, self.Ms, lams[0], slabs_to())
+                    zero = self._workspace("pool_zero_planes", (2 * sp.Cp,))
+                    zero.zero_()
+                    pool = pool.interior(zero)
                 for r0 in range(0, Mrun, Rb):
                     R = min(Rb, Mrun - r0)
                     if pool is not None:
@@ -759,25 +795,58 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
                     if scr is not None:
                         for jj in range(len(lams)):
                             hip.convert(dst[jj], outs[jj][r0:r0 + R])
+                if half:
+                    keep_planes()
             self._timed("spectral_product", fl, lambda: product_rows(feed), valu=fv)
             # what the buffer's readers are owed of this operator's rows and the step did not store whole: the hand-over's interior planes,
             # and with the cross block from the magnetic rows A_g K_01, which the step did not run
             whole = feed is None or feed.store_all
             late = [j for j in props if (not step.sym or (s_, j) in kept) and not (whole and j in blocks)]
             if late:
-                step.ak_fill.append(lambda fill=product_rows, lams=[gen_of[j] for j in late], outs=[out_of[j] for j in late]:
-                                    fill(None, lams=lams, outs=outs))
+                # (half: the fill runs every gravity row whole, with its own boundary planes -- the launches of a step without the shortcut)
+                whole_rows = dict(Mrun=self.Ms, half=False) if half else {}
+                step.ak_fill.append(lambda fill=product_rows, lams=[gen_of[j] for j in late], outs=[out_of[j] for j in late], kw=whole_rows:
+                                    fill(None, lams=lams, outs=outs, **kw))
+
+    def _gram_feed_applies(self, step, blocks):
+        """The condition of _gram_feed for the blocks `blocks` of one operator's rows (nothing is allocated here)."""
+        gram, sp = self._gram, self._spectral_product()
+        funcs = ("grav", "magn")
+        return bool(gram_gx_route(self.feed, self.route.family, step.sym, self.f32, self.world, self.exchange, self.nx, self.ny, self.nz, sp.forms)
+                    and gram is not None and gram.gx_applies() and sp.gx_applies()
+                    and all(j in (0, 1) and self._lam.get(funcs[j]) is not None for j in blocks))
+
+    def _grav_mirror_rows(self, step, A_g):
+        """Gravity rows whose interior part a step of the symmetric plan runs when the interior part of AkA's gravity block comes from
+        half its rows ("gravity block from half its rows"): ceil(Ms / 2) rounded up to the spectral product's batch, as
+        _mirror_rows; 0: every row runs whole.  plan.grav_mirror_route holds the gate."""
+        if not step.sym:                                      # (no symmetric plan: nothing to ask, and no spectral product need exist)
+            return 0
+        sp = self._spectral_product()
+        hit, lam = self._mirror.get("grav"), self._lam.get("grav")
+        static = hit is not None and hit[0] is A_g            # (measured only where _mirror_static held; what it measured is not asked)
+        even = lam is not None and lam[0] is A_g              # (LatticeGram.eigen accepted the stencil table of exactly this operator)
+        # interior planes and boundary slabs of a row can be fed apart: the pooled feed of an implicit operator, or resident fp64 rows
+        # (copied a batch at a time with their two boundary planes zeroed: the same operands, so the two forms agree bit for bit)
+        if isinstance(A_g, StreamedOperator):
+            pooled = A_g.lattice is not None and A_g.lattice.jy is not None and sp.pool_applies()
+        else:
+            pooled = not self.f32
+        pooled = bool(pooled and (self.c0, self.c1) == (0, self.nx * self.ny * self.nz))
+        handover = bool(step.sym and 0 in step.props and self._gram_feed_applies(step, [0]))
+        alone = step.cross_rows == "magn"                     # (otherwise block K_01 needs every gravity row whole)
+        if not grav_mirror_route(self.grav, step.sym, static, handover, pooled, even, alone, self.nx, self.ny, self.nz):
+            return 0
+        return min(self.Ms, ((self.Ms + 1) // 2 + sp.R - 1) // sp.R * sp.R)
 
     def _gram_feed(self, step, s_, blocks):
         """The hand-over of x-analysed rows from the A K product of operator s_ to the lattice Gram (options.gram_gx; DESIGN.md 2,
         "x step in the A K inverse"), or None where the route does not apply: the symmetric plan of the one-rank `single` family, fp64
         assembly, both operators' Gram on the stencil eigen-data, 64 x 64 (x, z) planes.  Block j of A K meets operator j in AkA."""
-        gram, sp = self._gram, self._spectral_product()
-        funcs = ("grav", "magn")
-        if not (gram_gx_route(self.feed, self.route.family, step.sym, self.f32, self.world, self.exchange, self.nx, self.ny, self.nz, sp.forms)
-                and gram is not None and gram.gx_applies() and sp.gx_applies() and all(j in (0, 1) and self._lam.get(funcs[j]) is not None for j in blocks)):
+        gram, funcs = self._gram, ("grav", "magn")
+        if not self._gram_feed_applies(step, blocks):
             return None
-        S = [self._workspace("gram_S_%d%d" % (s_, j), (self.Ms * gram.Py * gram.Px,)) for j in blocks]
+        S =[self._workspace("gram_S_%d%d" % (s_, j), (self.Ms * gram.Py * gram.Px,)) for j in blocks]
         for j, Sj in zip(blocks, S):
             step.gram_S[(s_, j)] = Sj
         # AkA is the only reader of these rows inside a step (DESIGN.md 2, "Unwritten rows"): of A K the product stores the two
@@ -1041,8 +1110,11 @@ class PosteriorEngine(RowFormMixin, TransposedPosteriorMixin, ColumnExchangeMixi
         M_pad = step.M_pad
         step.mirror = self._mirror_rows(step, A_m)
         step.cross_rows = "magn" if cross_rows_route(self.cross, step.sym, step.mirror, self.nx, self.ny, self.nz) else "grav"
+        step.grav_mirror = self._grav_mirror_rows(step, A_g)
         for f, rec in self.aka_mirror.items():
-            rec["taken"] = bool(f == "magn" and step.mirror)      # (only the magnetic block has a mirrored form; gravity measures "no")
+            # (magnetic: the whole block is the mirror of its first half, by measurement; gravity: the interior part only, by the Gram's
+            # evenness check of the stencil table -- the record's table / slabs deviations are kept beside it, the slabs ungated)
+            rec["taken"] = bool(step.mirror if f == "magn" else step.grav_mirror)
         AK = self._assemble_AK(step, A_g, A_m)
         self.step_route = "rows" if step.rowpath else ("single" if step.sym else "columns")
         t = self._tick("ak_fused", t)

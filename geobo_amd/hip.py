@@ -261,6 +261,30 @@ def mirror_planes(src, dst, m, r0, r1, nx, nz):
     return dst
 
 
+def sym_add(E, B, n):
+    """B[r, c] += E[r, c] + E[c, r] for r, c < n (geobo_sym_add).  E, B: 2-D row-major views of at least n x n that do not overlap."""
+    lib = require_gpu()
+    lde, ldb = _rowmajor(E, "E"), _rowmajor(B, "B")
+    assert min(E.shape) >= n and min(B.shape) >= n
+    _lib.check(lib.geobo_sym_add(int(n), _p(E), int(lde), _p(B), int(ldb), _stream()), "geobo_sym_add")
+    return B
+
+
+def slab_pair_y(ny, C, rows, src, tab, out, plane=None):
+    """out[r, 0] = t(0) src[r, 0] + t(ny-1) src[r, 1], out[r, 1] = t(ny-1) src[r, 0] + t(0) src[r, 1] per mode c < C, t(d) = tab[d*C + c]
+    (geobo_slab_pair_y): the y stage of rows that are zero between their boundary planes.  src, out: [rows][2][plane] (row-major
+    (rows, >= 2 plane) views, or flat buffers of rows of 2 plane doubles); tab: the generator table [ny][C]."""
+    lib = require_gpu()
+    plane = int(C if plane is None else plane)
+    ld = lambda t: t.stride(0) if t.dim() == 2 else 2 * plane
+    room = lambda t: _chk(t, "planes").untyped_storage().nbytes() // 8 - t.storage_offset()
+    assert all(t.dim() == 1 or t.stride(1) == 1 for t in (src, out)) and _chk(tab, "tab").is_contiguous() and tab.numel() >= ny * C
+    assert rows == 0 or min(room(src) - (rows - 1) * ld(src), room(out) - (rows - 1) * ld(out)) >= plane + C
+    _lib.check(lib.geobo_slab_pair_y(int(ny), int(C), plane, int(rows), _p(src), int(ld(src)), _p(tab), _p(out), int(ld(out)), _stream()),
+               "geobo_slab_pair_y")
+    return out
+
+
 def mirror_dev_ws_doubles():
     return require_gpu().geobo_mirror_dev_ws_bytes() // 8
 

@@ -140,6 +140,42 @@ def cross_rows_route(opts, sym, mirror_rows, nx, ny, nz):
     return opts.cross_rows == "magn" or nx == ny == nz == 64
 
 
+# AkA's gravity block from half its rows (engine._grav_mirror_rows, transposed._assemble_AkA_sym; DESIGN.md section 2, "gravity block
+# from half its rows"): resolved once per engine from the same mapping, in a table of its own like the two above.
+GRAV_MIRROR = ("auto", "on", "off")
+
+
+def _grav_mirror(v):
+    if v not in GRAV_MIRROR:
+        raise ValueError("GEOBO_GRAV_MIRROR must be one of %s, got %r" % (", ".join(GRAV_MIRROR), v))
+    return v
+
+
+GRAV_OPTIONS = {"grav_mirror": ("GEOBO_GRAV_MIRROR", "auto", _grav_mirror)}     # "on": wherever the gate holds; "off": every gravity row runs
+GravOptions = make_dataclass("GravOptions", [(k, type(d)) for k, (_, d, _p) in GRAV_OPTIONS.items()], frozen=True)
+
+
+def grav_options(env=None):
+    """GravOptions from an environment-like mapping (None: every default)."""
+    env = {} if env is None else env
+    return GravOptions(**{k: parse(env[var]) if var in env else default for k, (var, default, parse) in GRAV_OPTIONS.items()})
+
+
+def grav_mirror_route(opts, sym, static, handover, pooled, even, alone, nx, ny, nz):
+    """Whether a step builds the interior part of AkA's gravity block from the first half of the gravity rows and mirrors the rest.
+    The gate is a set of conditions, none of them a tuning value: the symmetric plan (sym); the static conditions of the point
+    mirror (static: engine._mirror_static held when the operator was built); the A K product hands its rows to the lattice Gram
+    (handover: engine._gram_feed applies) and can feed interior and boundary planes apart (pooled: the plane pool of an implicit
+    operator, or resident fp64 rows copied with their boundary planes zeroed -- the same operands, the same bits); the gravity stencil table passed the Gram's evenness check (even: LatticeGram.eigen returned eigen-data -- evenness in
+    both offsets implies point evenness); the gravity rows run block K_00 alone (alone: the cross block comes from the magnetic
+    rows, cross_rows_route -- block K_01 of the gravity rows would need every row whole).  The boundary slabs are not asked anything:
+    their terms are computed with no symmetry assumed.  "auto" takes it on the planner's cube only (nx = ny = nz = 64), the
+    roll-out convention of cross_rows_route."""
+    if opts.grav_mirror == "off" or not (sym and static and handover and pooled and even and alone):
+        return False
+    return opts.grav_mirror == "on" or nx == ny == nz == 64
+
+
 def half_integer(n):
     """True where the axis runs on the HALF-INTEGER (skew-circulant) basis (round 6): a symmetric Toeplitz block of size n is also the
     leading block of the skew-circulant of size P = 2n (first column k_0 .. k_{n-1}, *, -k_{n-1} .. -k_1), diagonalised by cos / sin of

@@ -199,12 +199,18 @@ class PooledRows:
     them in place (geobo_spectral_y_lattice), no forward transform per row.  pool: [nx][2ny-3][Cp] then the boundary planes [Ms][2][Cp]
     (`edge`, a view of the same buffer); row_off: int64 device offsets of the windows; jy / jx: host lattice indices (sweep order)."""
 
-    def __init__(self, pool, row_off, edge, jy, jx, r0=0, geo=None):
+    def __init__(self, pool, row_off, edge, jy, jx, r0=0, geo=None, edge_row=None):
         self.pool, self.row_off, self.edge, self.jy, self.jx, self.r0 = pool, row_off, edge, jy, jx, int(r0)
         self.geo = geo if geo is not None else (jy.tobytes(), jx.tobytes())      # the survey's identity for the product's table cache
+        self.edge_row = edge_row         # doubles between the boundary planes of consecutive rows (None: two planes, as plane_pool lays them out)
 
     def rows(self, r0):
-        return PooledRows(self.pool, self.row_off, self.edge, self.jy, self.jx, self.r0 + r0, self.geo)
+        return PooledRows(self.pool, self.row_off, self.edge, self.jy, self.jx, self.r0 + r0, self.geo, self.edge_row)
+
+    def interior(self, zero_planes):
+        """The same rows restricted to their interior planes 1 .. ny-2 (A_i of DESIGN.md 2, "gravity block from half its rows"): every
+        row reads zero_planes, two zero planes of the pool's stride, as its planes 0 and ny-1 (row stride 0)."""
+        return PooledRows(self.pool, self.row_off, zero_planes, self.jy, self.jx, self.r0, self.geo, 0)
 
 
 class ConvolvedRows:
@@ -321,6 +327,27 @@ class SpectralProduct:
         rows.row_off = row_off
         return rows
 
+    def slab_spectra(self, A, Ms):
+        """[Ms][2][Cp] (x, z)-spectra of the planes 0 and ny-1 of the first Ms rows of a resident operator: what plane_pool keeps behind
+        the interior pool for an implicit one (the same forward launch on the same planes)."""
+        nx, ny, nz, Cp = self.nx, self.ny, self.nz, self.Cp
+        assert self.forms.xz == "fold" and A.stride(1) == 1
+        spec = self.buf("SlabSpec", Ms * 2 * Cp)
+        hip.xz2d_fold(False, nx, Ms, 2, A, A.stride(0), (ny - 1) * nx * nz, self.F["x"], self.F["z"], spec, 2 * Cp, Cp)
+        return spec
+
+    def slab_pair_rows(self, edge_spec, Ms, gen, out):
+        """out[r, k nx nz:(k+1) nx nz] = plane (0, ny-1)[k] of (A_s K)[r] for r < Ms, A_s the rows of an operator restricted to their two
+        boundary planes, given by those planes' spectra edge_spec [Ms][2][Cp] (PooledRows.edge, slab_spectra), K the block with
+        generators gen: the 2 x 2 y stage (geobo_slab_pair_y), then the storing inverse transform of those 2 Ms planes.  (The other
+        planes of A_s K are not computed: AkA's slab-slab term reads these two only.)"""
+        nx, ny, nz, C, Cp = self.nx, self.ny, self.nz, self.Px * self.Pz, self.Cp
+        assert self.forms.xz == "fold" and out.stride(1) == 1 and out.shape[1] >= 2 * nx * nz
+        spec = self.buf("S", Ms * 2 * Cp)
+        hip.slab_pair_y(ny, C, Ms, edge_spec, gen, spec, plane=Cp)
+        hip.xz2d_fold(True, nx, Ms, 2, spec, 2 * Cp, Cp, self.F["x"], self.F["z"], out, out.stride(0), nx * nz)
+        return out
+
     def _pool_batch(self, A, R):
         """(device int32 sweep order, distinct planes) of the first R rows of a pooled operator (constants of the survey: kept)."""
         a = A.r0
@@ -337,7 +364,8 @@ class SpectralProduct:
         ny, C, Cp = self.ny, self.Px * self.Pz, self.Cp
         order, distinct = self._pool_batch(A, R)
         a = A.r0
-        fn = lambda: hip.spectral_y_lattice(ny, C, R, A.pool, A.row_off[a:], A.edge[a * 2 * Cp:], 2 * Cp, order, tabs, outs, y0, y1, plane=Cp)
+        er = 2 * Cp if A.edge_row is None else A.edge_row
+        fn = lambda: hip.spectral_y_lattice(ny, C, R, A.pool, A.row_off[a:], A.edge[a * er:], er, order, tabs, outs, y0, y1, plane=Cp)
         name = "kernel:toeplitz_y" if len(tabs) >= 2 else "kernel:toeplitz_y_single"
         return self._launch(name, 8.0 * C * (distinct + R * len(tabs) * (y1 - y0)), R, self.y_stage_flop(1, len(tabs), y1 - y0), fn)
 

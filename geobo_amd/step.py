@@ -91,9 +91,12 @@ class Step:
     rowpath: bool = False       # the row-sharded form: no A K at all
     mirror: int = 0             # > 0 (sym only): magnetic rows the assembly runs; the rest of AkA's magnetic block is their point mirror
     cross_rows: str = "grav"    # rows behind AkA's cross block: "grav" (A_g K_01, all rows) | "magn" (A_m K_10, the step.mirror rows; plan.cross_rows_route)
+    grav_mirror: int = 0        # > 0 (sym only): gravity rows whose interior part A_i K the assembly runs (plan.grav_mirror_route); 0: all rows, whole
     # left for the later stages
     gens: dict = field(default_factory=dict)        # Toeplitz generators of the covariance blocks (s, j)
     fullrows: dict = field(default_factory=dict)    # column form with the row exchange: this rank's whole rows of A K
     gram_S: dict = field(default_factory=dict)      # (s, j) -> the lattice Gram's scaled spectra of the block's rows (engine._gram_feed)
+    grav_slabs: object = None                       # grav_mirror: planes 0 and ny-1 of A_s K_00, [Ms][2 nx nz] (engine._assemble_AK_spectral)
+    grav_iplanes: object = None                     # grav_mirror: planes 0 and ny-1 of A_i K_00, [Ms][2 nx nz], the run rows stored, the rest mirrored in AkA
     ak_fill: list = field(default_factory=list)     # storing products that write the interior planes of A K the hand-over skipped (run by
                                                     # engine.last's completion hook, on the first read of the buffer)

@@ -75,8 +75,33 @@ class TransposedPosteriorMixin:
             slabs(X, Ms, 0, out)
             hip.transpose(AkA[Msp:2 * Msp, :Msp], AkA[:Msp, Msp:2 * Msp])
 
+        # step.grav_mirror: A K holds the interior part A_i K of the first rows of the gravity block, boundary planes only
+        Mg = step.grav_mirror or self.Ms
+
+        def grav_from_half():
+            """AkA[grav rows, grav columns] from A_g = A_i + A_s, interior planes and boundary slabs ("gravity block from half
+            its rows"):  A_i K A_i^T + E + E^T + A_s K A_s^T  with  E = A_i K A_s^T.  The first term is centrosymmetric -- the stencil
+            table is even, which the Gram's eigen-data require -- so the step.grav_mirror rows the product ran give it whole.  E takes the
+            boundary planes of A_i K for every row (the mirrored rows': the x-reversed opposite planes of their partners) against the
+            slab spectra, no symmetry assumed; the last term the two planes of A_s K the product left in step.grav_slabs."""
+            P, out, Ms = step.grav_iplanes, AkA[0:, 0:Msp], self.Ms          # (P: the two planes of A_i K, kept apart from the A K buffer)
+            gram.back_rows(S[(0, 0)], Mg, out)
+            hip.centro_fill(out[:Ms, :Ms], Ms, (Ms + 1) // 2)
+            for dst, src in ((0, 1), (1, 0)):
+                hip.mirror_planes(P[:, src * pl:(src + 1) * pl], P[:, dst * pl:(dst + 1) * pl], Ms, 0, Ms - Mg, self.nx, self.nz)
+            E = self._workspace2d("grav_E", Ms, Ms)
+            E.zero_()
+            for k, iy in enumerate((0, ny - 1)):
+                gram.edge_rows(P[:, k * pl:], Ms, self._edge_spectrum("grav", k, edge_cols(0, k, iy)), E)
+            hip.sym_add(E, out[:Ms, :Ms], Ms)
+            for k, iy in enumerate((0, ny - 1)):
+                gram.edge_rows(step.grav_slabs[:, k * pl:], Ms, self._edge_spectrum("grav", k, edge_cols(0, k, iy)), out)
+
         def run():
-            rows_times_AT(blk(0, 0), self.Ms, 0, AkA[0:, 0:Msp], S.get((0, 0)))
+            if step.grav_mirror:
+                grav_from_half()
+            else:
+                rows_times_AT(blk(0, 0), self.Ms, 0, AkA[0:, 0:Msp], S.get((0, 0)))
             if not cross:
                 rows_times_AT(blk(0, 1), self.Ms, 1, AkA[0:, Msp:2 * Msp], S.get((0, 1)))
             rows_times_AT(blk(Msp, 1), Mm, 1, AkA[Msp:, Msp:2 * Msp], S.get((1, 1)))
@@ -88,8 +113,8 @@ class TransposedPosteriorMixin:
                 rows_times_AT(blk(off_d, 0), Md, 0, AkA[off_d:, 0:Msp])
                 rows_times_AT(blk(off_d, 1), Md, 1, AkA[off_d:, Msp:2 * Msp])
         S = step.gram_S
-        nfed = sum(self.Ms if s_ == 0 else Mm for s_, _ in S)
-        self._timed("aka_lattice", gram.flops((self.Ms + 2 * Mm if cross else 2 * self.Ms + Mm) + 2 * Md - nfed, ny) + gram.flops_back(nfed), run)
+        nfed = sum(Mg if s_ == 0 else Mm for s_, _ in S)
+        self._timed("aka_lattice", gram.flops((Mg + 2 * Mm if cross else 2 * self.Ms + Mm) + 2 * Md - nfed, ny) + gram.flops_back(nfed), run)
         if step.mirror:
             # (after gram_rows AND edge_rows of the block: the fill copies finished rows; same stream, so it is ordered behind them)
             self._timed("aka_centro_fill", 0.0, lambda: hip.centro_fill(AkA[Msp:Msp + self.Ms, Msp:Msp + self.Ms], self.Ms, (self.Ms + 1) // 2))

@@ -609,6 +609,20 @@ int geobo_mirror_rows(double* X, int64_t ld, int64_t m, int64_t r0, int64_t nb, 
  * (GEOBO_E_ARG, also for a null pointer); nz, lds, ldd even, src, dst 16-byte aligned (GEOBO_E_ALIGN). */
 int geobo_mirror_planes(const double* src, int64_t lds, double* dst, int64_t ldd, int64_t m, int64_t r0, int64_t r1, int nx, int nz,
                         void* stream);
+/* Additive, version unchanged.  B[r][c] += E[r][c] + E[c][r] for r, c < n: a term and its transpose added to a square block in one
+ * pass (AkA's gravity block from half its rows, DESIGN.md section 2: E = A_i K A_s^T from one sweep of the boundary-slab stage).
+ * Tiled like geobo_transpose, one owner per element of B, no atomics.  E and B must not overlap.  n <= lde, ldb (GEOBO_E_ARG, also
+ * for a null pointer). */
+int geobo_sym_add(int64_t n, const double* E, int64_t lde, double* B, int64_t ldb, void* stream);
+/* Additive, version unchanged.  The y stage of rows that live on their two boundary planes only (the boundary-slab part A_s of a
+ * lattice operator): per mode c < C the symmetric Toeplitz block meets the row in four entries,
+ *     out[r][0][c] = t_c(0) in[r][0][c] + t_c(ny-1) in[r][1][c],   out[r][1][c] = t_c(ny-1) in[r][0][c] + t_c(0) in[r][1][c]
+ * with t_c(d) = tab[d*C + c] (the generator table [ny][C] of geobo_toeplitz_y) and index 0 / 1 = the planes y = 0 / ny-1, `plane`
+ * doubles apart; rows in_row / out_row apart.  Modes behind C are neither read nor written.  in and out must not overlap.
+ * ny >= 2, C <= plane, 2 plane <= in_row, out_row (GEOBO_E_ARG); C, plane, in_row, out_row even, in, tab, out 16-byte aligned
+ * (GEOBO_E_ALIGN). */
+int geobo_slab_pair_y(int ny, int64_t C, int64_t plane, int64_t rows, const double* in, int64_t in_row, const double* tab, double* out,
+                      int64_t out_row, void* stream);
 /* Whether an operator HAS that symmetry is measured, not assumed:
  *     out2[0] = max |a[r][x][z] - b[rows-1-r][nx-1-x][z]|,   out2[1] = max(|a|, |b|)   over r < rows, x < nx, z < nz
  * (a NaN in either makes the result NaN).  a, b: rows of nx nz doubles, lda / ldb apart.  For the stencil table
